@@ -26,6 +26,11 @@ Inputs are resident in HBM before the timed region.  value = pictures / second (
 Contract: python bench.py --gpus N --steps K --warmup W ; for N>1 launched by torch.distributed.run, one rank per GPU;
 GOP segments are independent (closed GOPs) so ranks share nothing and the only collectives are the
 timing barrier / max-reduce.  --preset c1 | c2 | c3 | c5 selects the BASELINE.json configuration (default c3, the one `metric` is quoted on).
+
+A plain run does only what `value` / `ms_per_step` need: set-up, warm-up, the K timed steps, the result line.  --full adds every other leg
+(the public-API path, the intra-pass timing, the G = 1 runs, the reference flags, the step without key frames, ME alone, the workload
+statistics and the CPU baseline).  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32 /
+float64, a fixed seeded sample of the larger arrays; the inputs are the same from run to run for the same arguments).
 """
 import argparse
 import ctypes as C
@@ -427,6 +432,9 @@ def main():
                     "first GOP to the next rank (RCCL send / recv over xGMI), the one exchange step of the path; closed GOPs (the default) need none")
     ap.add_argument("--no-key-frames", action="store_true", help="profiling aid: inter pictures only (the round-4 step); `value_inter_only` is measured either way")
     ap.add_argument("--stages", default=",".join(STAGES), help="profiling aid: pa, me and / or the EncDec chain (any of mc..pad runs the whole chain)")
+    ap.add_argument("--full", action="store_true", help="also every leg beyond the headline figure: public-API path, intra-pass timing, G = 1 runs, "
+                    "reference flags, step without key frames, ME alone, workload statistics, CPU baseline (--no-* narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -464,7 +472,7 @@ def main():
     # stream -- with its ~dozen hardware queues alive beside the caller's (torch keeps a stream pool for the life of the process) the 40 ms runs
     # came out 10-25 % lower and noisy (2 500-3 200 against 3 150-3 190 alone, tools/r06_api.py).
     early_legs = {}
-    if not args.no_extras and rank == 0 and world == 1 and ((Wd, Hd) == (W4K, H4K) or os.environ.get("SVT_BENCH_API_PATH")):
+    if args.full and not args.no_extras and rank == 0 and world == 1 and ((Wd, Hd) == (W4K, H4K) or os.environ.get("SVT_BENCH_API_PATH")):
         api = api_path_rate(T.gen_clip(Wd, Hd, MINIGOP + 1, seed=GS.gop_seed(11, 0)), Wd, Hd, enc_mode, tune)   # (GOP 0's pictures, as frames0 below)
         if api is not None:
             early_legs["api_path"] = api
@@ -893,29 +901,32 @@ def main():
     for grp in P_main["groups"]:
         cnt = (C.c_int32 * 8)()
         B.check(lib.svt_hip_encdec_work_status(grp["ctx"], grp["work"], cnt))     # synchronises; raises on a malformed grid
-    resid_acc, eob_by_size = [], [[] for _ in range(4)]
-    with torch.no_grad():
-        for i in range(1, MINIGOP + 1):
-            sy, py = d_src[0, i, :Wd * Hd].to(torch.int16), d_pred[0, i - 1, :Wd * Hd].to(torch.int16)
-            resid_acc.append((sy - py).abs().to(torch.float32).mean().item())
-            em = d_emap[0, i - 1, :(Wd // 4) * (Hd // 4)].cpu().numpy().view(np.uint16).reshape(Hd // 4, Wd // 4)
-            k4 = np.kron(kcell[0][i], np.ones((2, 2), np.int64))[:Hd // 4, :Wd // 4]
-            y4, x4 = np.meshgrid(np.arange(Hd // 4), np.arange(Wd // 4), indexing="ij")
-            for k in range(4):
-                n4 = 1 << k
-                eob_by_size[k].append(em[(k4 == k) & (y4 % n4 == 0) & (x4 % n4 == 0)].astype(np.int64))
-    skip_share = float(np.mean([d_lf[0][i].cpu().numpy().view(B.LF_MODE_INFO_DTYPE)["skip"].mean() for i in range(1, MINIGOP + 1)]))
-    workload_stats = {"mean_abs_luma_residual_gop0": round(float(np.mean(resid_acc)), 2),
-                      "mean_luma_eob_by_tx_size": [round(float(np.concatenate(eob_by_size[ts]).mean()), 1) if sum(len(a) for a in eob_by_size[ts]) else None for ts in range(4)],
-                      "transform_blocks_by_tx_size_per_step": [int(v) for v in blocks_by_size],
-                      # the synthesised partition: share of the step's transform blocks / of its samples per transform size (4x4, 8x8, 16x16, 32x32)
-                      "tx_size_share_of_blocks": [round(float(v) / max(1, int(blocks_by_size.sum())), 3) for v in blocks_by_size],
-                      "tx_size_share_of_samples": [round(float(v) * (16 << (2 * k_)) / max(1.0, float(sum(int(b_) * (16 << (2 * j_)) for j_, b_ in enumerate(blocks_by_size)))), 3)
-                                                   for k_, v in enumerate(blocks_by_size)],
-                      "skip_block_share_gop0": round(skip_share, 3)}
+    workload_stats = None
+    if args.full:
+        resid_acc, eob_by_size = [], [[] for _ in range(4)]
+        with torch.no_grad():
+            for i in range(1, MINIGOP + 1):
+                sy, py = d_src[0, i, :Wd * Hd].to(torch.int16), d_pred[0, i - 1, :Wd * Hd].to(torch.int16)
+                resid_acc.append((sy - py).abs().to(torch.float32).mean().item())
+                em = d_emap[0, i - 1, :(Wd // 4) * (Hd // 4)].cpu().numpy().view(np.uint16).reshape(Hd // 4, Wd // 4)
+                k4 = np.kron(kcell[0][i], np.ones((2, 2), np.int64))[:Hd // 4, :Wd // 4]
+                y4, x4 = np.meshgrid(np.arange(Hd // 4), np.arange(Wd // 4), indexing="ij")
+                for k in range(4):
+                    n4 = 1 << k
+                    eob_by_size[k].append(em[(k4 == k) & (y4 % n4 == 0) & (x4 % n4 == 0)].astype(np.int64))
+        skip_share = float(np.mean([d_lf[0][i].cpu().numpy().view(B.LF_MODE_INFO_DTYPE)["skip"].mean() for i in range(1, MINIGOP + 1)]))
+        workload_stats = {"mean_abs_luma_residual_gop0": round(float(np.mean(resid_acc)), 2),
+                          "mean_luma_eob_by_tx_size": [round(float(np.concatenate(eob_by_size[ts]).mean()), 1) if sum(len(a) for a in eob_by_size[ts]) else None
+                                                       for ts in range(4)],
+                          "transform_blocks_by_tx_size_per_step": [int(v) for v in blocks_by_size],
+                          # the synthesised partition: share of the step's transform blocks / of its samples per transform size (4x4, 8x8, 16x16, 32x32)
+                          "tx_size_share_of_blocks": [round(float(v) / max(1, int(blocks_by_size.sum())), 3) for v in blocks_by_size],
+                          "tx_size_share_of_samples": [round(float(v) * (16 << (2 * k_)) / max(1.0, float(sum(int(b_) * (16 << (2 * j_)) for j_, b_ in enumerate(blocks_by_size)))), 3)
+                                                       for k_, v in enumerate(blocks_by_size)],
+                          "skip_block_share_gop0": round(skip_share, 3)}
     step_no = [1]   # the setup pass was step 0 (mini-GOP 0 complete in ring slot 0)
-    extras = not args.no_extras and rank == 0
-    P_single = None if (args.no_single or rank != 0) else build_pipeline([0], single_pairs, split="picture")
+    extras = args.full and not args.no_extras and rank == 0
+    P_single = None if (not args.full or args.no_single or rank != 0) else build_pipeline([0], single_pairs, split="picture")
     P_ref = build_pipeline(all_gops, grp_pairs, recon_file=0) if extras else None
     P_inter = build_pipeline(all_gops, grp_pairs, keys=False) if (extras and P_main["keys"]) else None
     setup_s = time.perf_counter() - t_setup0
@@ -1065,7 +1076,8 @@ def main():
         S = make_state()
         if schedule == "diagonal":
             warmup = max(warmup, n_layers)   # the pipeline of n_layers mini-GOPs has to fill
-        n_calls = sum(len(grp["diag"]) + sum(len(w_) for w_ in grp["waves"]) for grp in P["groups"])
+        # driver calls per step of this schedule: the pool below is made before the clock starts and grows with the steps
+        n_calls = sum(len(grp["diag"]) if schedule == "diagonal" else sum(len(w_) for w_ in grp["waves"]) for grp in P["groups"])
         pool = EventPool(steps * (2 * len(P["me_sets"][0]) + 2 + 8 * n_calls) + 16)
         for _ in range(warmup):
             step(P, S, schedule)
@@ -1096,6 +1108,59 @@ def main():
         me_launches = [(e0.elapsed_time(e1)) for name, sid, e0, e1 in S["ev"] if name == "me"]
         return dt, t_enq / n_free, stage_ms, stage_ms_sum, me_launches
 
+    def dump_outputs(out_dir):
+        """What the main pipeline's last timed step computed, as DIR/<name>.npy (float32; float64 for the ME results), about 58 MB at
+        2160p: the whole luma plane of GOP 0's newest base-layer reconstruction, and a fixed, seeded sample (sorted positions, the same
+        for the same sizes) of each of the step's other outputs: every reconstruction it wrote (padded Y, Cb, Cr), the key frame it
+        coded, the quantised coefficients, eob maps, loop-filter masks, non-zero maps and skip flags of every picture, and the ME
+        results of the newest mini-GOP."""
+        import zlib
+        os.makedirs(out_dir, exist_ok=True)
+        ph = (step_no[0] - 1) % RING       # ring slot of the newest mini-GOP of the last step
+        total = [0]
+
+        def save(name, a, dtype=np.float32):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            total[0] += a.nbytes
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+        def positions(name, n, k):
+            return np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, min(k, n)))
+
+        def gather(t, flat):
+            return t.reshape(-1)[torch.from_numpy(flat).to(dev)].cpu().numpy()
+
+        def save_rows(name, t, rows, row_len, k):
+            """k sampled elements of the rows `rows` (each row_len elements long) of the flat device tensor t"""
+            rows = np.asarray(rows, np.int64)
+            idx = positions(name, len(rows) * row_len, k)
+            save(name, gather(t, rows[idx // row_len] * row_len + idx % row_len))
+
+        full_rows = min(Hd, 8_294_400 // Wd)   # (at most a 2160p plane)
+        y = d_rec[ph, 0, MINIGOP - 1, :geo.u_base].view(geo.ph, geo.pw)[PAD:PAD + full_rows, PAD:PAD + Wd]
+        save("recon_luma_gop0_base", y.cpu().numpy())
+        batches = [bt for grp in P_main["groups"] for bt in (grp["diag"] if args.schedule == "diagonal" else sum(grp["waves"], []))]
+        pics = sorted({(((ph - back) % RING) * G + g) * MINIGOP + i - 1 for bt in batches for g, i, back in bt["items"]})
+        save_rows("recon_sample", d_rec, pics, geo.rec_bytes, 1 << 20)
+        if P_main["keys"]:
+            kb = key_buf(ph + KEY_LEAD)
+            kg = [g for g in all_gops if ((ph + KEY_LEAD) % RING) % KEYP == g % KEYP]
+            if kg:
+                save_rows("key_recon_sample", d_key, [g * 2 + kb for g in kg], geo.rec_bytes, 1 << 19)
+        save("qcoeff_sample", gather(d_q, positions("qcoeff_sample", d_q.numel(), 1 << 20)))
+        save("eob_map_sample", gather(d_emap, positions("eob_map_sample", d_emap.numel(), 1 << 19)).view(np.uint16))
+        save("lf_mask_sample", gather(d_lfm, positions("lf_mask_sample", d_lfm.numel(), 1 << 19)))
+        save("nz_map_sample", gather(d_nz, positions("nz_map_sample", d_nz.numel(), 1 << 19)))
+        lmi = torch.stack([d_lf[g][i] for g in all_gops for i in range(1, MINIGOP + 1)]).view(-1, B.LF_MODE_INFO_DTYPE.itemsize)
+        recs = positions("skip_flags_sample", lmi.shape[0], 1 << 19)
+        save("skip_flags_sample", gather(lmi, recs * B.LF_MODE_INFO_DTYPE.itemsize + B.LF_MODE_INFO_DTYPE.fields["skip"][1]))
+        me = torch.stack([results[g][i] for g in all_gops for i in range(1, MINIGOP + 1)]).view(-1, 10)
+        recs = positions("me_results_sample", me.shape[0], 1 << 16)
+        r = me[torch.from_numpy(recs).to(dev)].cpu().numpy().view(B.ME_RESULT_DTYPE).reshape(-1)
+        fields = [f for f in B.ME_RESULT_DTYPE.names if f != "pad"]
+        save("me_results_sample", np.stack([r[f] for f in fields], axis=1), np.float64)
+        assert total[0] <= 64_000_000, f"--dump-outputs wrote {total[0]} bytes"
+
     key_workgroups(int(os.environ.get("SVT_BENCH_KEY_WGS", "128")))
     dt, enq_s, stage_ms, stage_ms_sum, me_launch_list = timed_run(P_main, args.schedule, args.steps, args.warmup, True)
     n_keys_main = P_main["n_keys"]
@@ -1106,6 +1171,8 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs)
     single = {}
     if P_single is not None:
         k1 = max(4, args.steps)
@@ -1295,7 +1362,7 @@ def main():
                      "PCIe-inclusive rate of the public-API path is `api_path` (app/svt_enc_api_bench.c, DESIGN.md section 7)",
     }
     cpu_inputs = None
-    if not args.no_cpu_baseline and world == 1:   # the CPU leg runs at N = 1 only (rank 0's host cores are not shared with other ranks)
+    if args.full and not args.no_cpu_baseline and world == 1:   # the CPU leg runs at N = 1 only (rank 0's host cores are not shared with other ranks)
         lfm0 = {i: np.frombuffer(d_lfm[0, i - 1].cpu().numpy(), dtype=B.LF_MASK_DTYPE).reshape(sb_rows, sb_cols).copy() for i in range(1, MINIGOP + 1)}
         lf0 = {i: d_lf[0][i].cpu().numpy().view(B.LF_MODE_INFO_DTYPE).reshape(mi_rows, mi_cols).copy() for i in range(1, MINIGOP + 1)}   # with the skip flags
         ref_inputs = {"pred": d_pred[0, MINIGOP // 4 - 1].cpu().numpy(), "kcell": kcell[0][MINIGOP // 4], "level": level}
