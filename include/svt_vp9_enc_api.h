@@ -121,7 +121,8 @@ typedef struct svt_vp9_shim_picture_info {
     /* the stages behind mode decision (svt_encdec_flags of svtvp9_hip.h, as the reference derives them for this picture) */
     int32_t  is_used_as_reference, do_recon, apply_loop_filter, pad_reference;
     int32_t  q_index, filter_level;
-    int32_t  decision_source;      /* 0 built-in stand-in, 1 the host's callback */
+    int32_t  decision_source;      /* 0 built-in stand-in, 1 the host's callback, 2 the searched intra stand-in (an intra picture no callback
+                                      decided, with SVT_HIP_INTRA_DECISION=search: svt_hip_intra_search_device + svt_hip_md_intra_search_device) */
     int32_t  intra_recon_is_source; /* always 0 since round 4: intra pictures go through the intra encode pass on the GPU
                                       (svt_hip_encdec_intra_device); the field keeps the struct layout of round 3 */
     int32_t  device_ordinal;       /* the GPU that coded the picture's GOP */
@@ -152,7 +153,11 @@ EbErrorType svt_vp9_shim_get_counters(EbComponentType *svt_enc_component, uint64
  * blocks of 8x8 / 16x16 / 32x32 (sb_type 3 / 6 / 9, tx_size 1 / 2 / 3, is_inter 0) with pad_[1] = luma mode and pad_[2] = chroma mode;
  * units of four 4x4 blocks: sb_type 0, tx_size 0, their luma modes in the nibbles of pad_[1] (blocks 0, 1) and pad_[0] (blocks 2, 3)
  * (0 DC, 1 V, 2 H, 3 D45, 4 D135, 5 D117, 6 D153, 7 D207, 8 D63, 9 TM), svt_hip_encdec_intra_device of svtvp9_hip.h; the stand-in
- * for an intra picture is 16x16 blocks with DC prediction.  The grids of an INTER picture may hold intra blocks as well (is_inter 0 + modes in
+ * for an intra picture is 16x16 blocks with DC prediction (decision_source 0).  The environment variable SVT_HIP_INTRA_DECISION, read by
+ * eb_vp9_init_encoder for that encoder, replaces it: unset or "dc" as above; "search" = the open-loop intra search of the picture's
+ * source and the grid built from its costs (blocks 4x4 .. 32x32, all ten modes; NOT the reference's mode decision either; lambda = 4 x the
+ * ac quantiser step, the key-frame filter level; decision_source 2); any other value makes eb_vp9_init_encoder fail with
+ * EB_ErrorBadParameter.  The grids of an INTER picture may hold intra blocks as well (is_inter 0 + modes in
  * lf_mode_info, ref_list[0] = -1 in mc_mode_info) as long as the picture is reconstructed (info->do_recon; the reference's limit_intra
  * forbids intra blocks in the others): they are coded from their neighbours' reconstruction behind the inter blocks. */
 typedef int32_t (*svt_vp9_shim_md_callback)(void *user, const svt_vp9_shim_picture_info *info, const void *me_results, void *mc_mode_info,

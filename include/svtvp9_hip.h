@@ -809,6 +809,38 @@ int32_t svt_hip_encdec_intra_device(svt_hip_ctx *ctx, svt_encdec_work *work, con
 /* Stand-in decision for an intra picture (NOT the reference's): 16x16 blocks with DC prediction, 8x8 where a 16x16 block would
  * cross the picture edge. */
 int32_t svt_hip_md_intra_default_device(svt_hip_ctx *ctx, int32_t width, int32_t height, int32_t filter_level, svt_lf_mode_info *d_lf_mi, int32_t mi_stride);
+/* Open-loop intra search (OIS): the per-block, per-mode cost of every VP9 intra predictor, computed from the SOURCE samples (no
+ * reconstruction, so no dependency chain: the whole picture runs in parallel).  NOT the reference's mode decision; like the ME
+ * results, the records are the kind of input a host's mode decision consumes.
+ * For every square block of N in {4, 8, 16, 32} that lies wholly inside the picture and each of the ten modes, the prediction is
+ * built from the source with the rules of the intra encode pass (svt_hip_encdec_intra_device): left column 129 at x = 0, above row
+ * 127 at y = 0, corner 129 with an above row but no left column (127 at y = 0), no above-right samples for N >= 8 (the above row is
+ * replicated), a 4x4 block in the left half of its 8x8 unit reads the four true above-right samples.  sad = luma SAD of the best mode,
+ * ties to the lowest mode index.  For N >= 8 the chroma block (N / 2, both planes) is searched the same way: uv_mode = argmin of
+ * SAD_Cb + SAD_Cr, uv_sad = that sum.  Blocks that cross the right or bottom edge (and the parts of an incomplete SB outside the
+ * picture) get sad = uv_sad = UINT32_MAX, mode = uv_mode = 0xFF. */
+typedef struct svt_ois_block {   /* 12 bytes */
+    uint32_t sad;      /* luma SAD of the best mode; UINT32_MAX: block not inside the picture */
+    uint32_t uv_sad;   /* Cb SAD + Cr SAD of the best chroma mode (blocks >= 8x8; UINT32_MAX for 4x4 records) */
+    uint8_t  mode, uv_mode;  /* PREDICTION_MODE 0 DC .. 9 TM; 0xFF where the SAD is UINT32_MAX */
+    uint8_t  pad_[2];
+} svt_ois_block;
+#define SVT_OIS_PER_SB 340  /* 4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, each group in z-order inside the SB */
+/* d_out: n_sb * SVT_OIS_PER_SB records, SB raster order (device memory).  src: device planes (luma stride >= width, chroma stride >=
+ * width / 2).  Width and height multiples of 8.  Asynchronous on the context's stream. */
+int32_t svt_hip_intra_search_device(svt_hip_ctx *ctx, const svt_yuv_planes *src, int32_t width, int32_t height, svt_ois_block *d_out);
+/* Stand-in intra decision from the OIS records (NOT the reference's mode decision): cost of a coded block J = D + lambda, D = sad +
+ * uv_sad for blocks >= 8x8, and for a unit of four 4x4 blocks (sb_type 0) the sum of the four 4x4 sad + the 8x8 record's uv_sad.
+ * Bottom-up: 8x8 against its four 4x4 blocks, 16x16 against its four best 8x8 subtrees, 32x32 against its four best 16x16 subtrees;
+ * a parent replaces its children when J_parent <= sum J_children (ties to the larger block), never when its record is UINT32_MAX or
+ * it crosses the picture edge; compared in 64 bits.  No 64x64 (the intra pass does not take it).  Writes the grid of
+ * svt_hip_encdec_intra_device: sb_type 0 / 3 / 6 / 9, tx_size of the block's size, is_inter = skip = 0, luma modes in pad_[1]
+ * (nibbles of pad_[1] / pad_[0] for sb_type 0), chroma mode in pad_[2], filter_level as given.  d_ois: the records of
+ * svt_hip_intra_search_device.  svt_hip_md_intra_search_picture is the host form (same text, csrc/encdec_core.h). */
+int32_t svt_hip_md_intra_search_device(svt_hip_ctx *ctx, const svt_ois_block *d_ois, int32_t width, int32_t height, uint32_t lambda,
+                                       int32_t filter_level, svt_lf_mode_info *d_lf_mi, int32_t mi_stride);
+int32_t svt_hip_md_intra_search_picture(const svt_ois_block *ois, int32_t width, int32_t height, uint32_t lambda, int32_t filter_level,
+                                        svt_lf_mode_info *lf_mi, int32_t mi_stride);
 /* Profiling aid: `hook` is called on the enqueueing thread at every stage boundary of svt_hip_encdec_batch_device (before the
  * stage named is enqueued; SVT_ENCDEC_STAGE_END after the last), so that a host can record events of its own on the context's stream
  * and attribute the chain's time to its stages.  NULL removes it. */

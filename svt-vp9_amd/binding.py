@@ -146,6 +146,12 @@ class EncdecPicture(C.Structure):
 
 SB_COEFFS = 6144
 
+# svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
+OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
+assert OIS_BLOCK_DTYPE.itemsize == 12
+OIS_PER_SB = 340
+OIS_NONE = 0xFFFFFFFF
+
 # every symbol include/svtvp9_hip.h declares
 EXPORTS = [
     "svt_hip_sb_count", "svt_hip_input_resolution", "svt_hip_me_params_derive", "svt_hip_me_params_preset", "svt_hip_ctx_create", "svt_hip_ctx_create_on_stream", "svt_hip_ctx_create_cu_mask", "svt_hip_ctx_stream",
@@ -166,6 +172,7 @@ EXPORTS = [
     "svt_hip_md_default_picture", "svt_hip_lf_build_masks_device", "svt_hip_ctx_wait_marker", "svt_hip_host_alloc", "svt_hip_host_free",
     "svt_hip_mem_download_2d_async", "svt_hip_mem_copy_2d_device", "svt_hip_encdec_work_set_stage_hook", "svt_hip_me_params_same_launch", "svt_hip_me_kernel_instance", "svt_hip_ctx_set_intra_workgroups", "svt_hip_ctx_warm", "svt_hip_ctx_warm_scratch", "svt_hip_lf_reserve",
     "svt_hip_me_last_instance", "svt_hip_me_lds_bytes", "svt_hip_vp9_layer_qindex", "svt_hip_mem_upload_2d_direct", "svt_hip_mem_upload_wait", "svt_hip_host_unregister_all", "svt_hip_host_registry_retain", "svt_hip_host_registry_release",
+    "svt_hip_intra_search_device", "svt_hip_md_intra_search_device", "svt_hip_md_intra_search_picture",
 ]
 
 _lib = None

@@ -12,6 +12,8 @@
  *   svt_md_default_unit      NOT the reference's mode decision (out of scope): a deterministic stand-in that turns the ME results of
  *                            an SB into a valid mode-info grid so that the stages behind mode decision can run from the public API
  *                            without a host-supplied decision
+ *   svt_md_intra_search_unit the intra counterpart (NOT the reference's either): the records of the open-loop intra search
+ *                            (svt_ois_block) -> a grid of intra blocks 4x4 .. 32x32 with their modes
  */
 #ifndef SVT_ENCDEC_CORE_H
 #define SVT_ENCDEC_CORE_H
@@ -299,6 +301,66 @@ SVT_HD void svt_md_default_unit(const svt_me_pu_result *res, int r, int c, int s
     mc->mv_col[1] = (int16_t)(d == 2 ? 2 * p->x_mv_l1 : 0);
     lf->sb_type = (uint8_t)sb_type; lf->tx_size = (uint8_t)tx; lf->skip = 0; lf->is_inter = 1; lf->filter_level = (uint8_t)filter_level;
     lf->pad_[0] = lf->pad_[1] = lf->pad_[2] = 0;
+}
+
+/* The intra counterpart, from the open-loop intra search records of an SB (svt_ois_block, SVT_OIS_PER_SB of them: 32x32 at 0, 16x16 at 4,
+ * 8x8 at 20, 4x4 at 84, each group in z-order).  Also NOT the reference's mode decision: cost of a coded block J = D + lambda with
+ * D = sad + uv_sad (blocks >= 8x8) or, for a unit of four 4x4 blocks, the four 4x4 sad + the 8x8 record's uv_sad; bottom-up 8x8 against its
+ * 4x4 blocks, 16x16 against its four best 8x8 subtrees, 32x32 against its four best 16x16 subtrees, the parent when J_parent <= sum of the
+ * children (ties to the larger block).  A parent whose record is UINT32_MAX, or that crosses the picture edge, is never chosen.  64-bit
+ * sums: UINT32_MAX + lambda does not wrap.  Unit (r, c) of the SB at (sb_row, sb_col); the unit must lie inside the picture. */
+#define SVT_OIS_NONE 0xFFFFFFFFu
+SVT_HD uint64_t svt_ois_cost(const svt_ois_block *b, uint32_t lambda) { return (uint64_t)b->sad + b->uv_sad + lambda; }
+/* best J of the 8x8 unit (r, c) of the SB: its 8x8 block or its four 4x4 blocks (*as8: which) */
+SVT_HD uint64_t svt_ois_best8(const svt_ois_block *ois, int r, int c, uint32_t lambda, int *as8) {
+    const uint32_t         z = svt_zorder4(c, r);
+    const svt_ois_block   *b8 = &ois[20 + z], *b4 = &ois[84 + 4 * z];
+    const uint64_t         j4 = (uint64_t)b4[0].sad + b4[1].sad + b4[2].sad + b4[3].sad + b8->uv_sad + lambda;
+    const uint64_t         j8 = svt_ois_cost(b8, lambda);
+    *as8 = b8->sad != SVT_OIS_NONE && j8 <= j4;
+    return *as8 ? j8 : j4;
+}
+/* best J of the 16x16 area (r16, c16) (0..3) of the SB: its 16x16 block or its four best 8x8 subtrees (*as16: which) */
+SVT_HD uint64_t svt_ois_best16(const svt_ois_block *ois, int r16, int c16, int fits, uint32_t lambda, int *as16) {
+    uint64_t s = 0;
+    for (int k = 0; k < 4; k++) { int a8; s += svt_ois_best8(ois, 2 * r16 + (k >> 1), 2 * c16 + (k & 1), lambda, &a8); }
+    const svt_ois_block *b = &ois[4 + svt_zorder4(c16, r16)];
+    const uint64_t       j = svt_ois_cost(b, lambda);
+    *as16 = fits && b->sad != SVT_OIS_NONE && j <= s;
+    return *as16 ? j : s;
+}
+
+SVT_HD void svt_md_intra_search_unit(const svt_ois_block *ois, int r, int c, int sb_row, int sb_col, int mi_rows, int mi_cols, uint32_t lambda,
+                                     int filter_level, svt_lf_mode_info *lf) {
+    const int ur0 = sb_row * 8, uc0 = sb_col * 8;
+    const int r32 = r >> 2, c32 = c >> 2, r16 = r >> 1, c16 = c >> 1;
+    const int fit32 = ur0 + 4 * r32 + 4 <= mi_rows && uc0 + 4 * c32 + 4 <= mi_cols;
+    /* the 32x32 area of this unit at its best: the 32x32 block or its four best 16x16 subtrees */
+    uint64_t s32 = 0;
+    int      as16_here = 0;
+    for (int k = 0; k < 4; k++) {
+        const int rr = 2 * r32 + (k >> 1), cc = 2 * c32 + (k & 1);
+        const int fits = ur0 + 2 * rr + 2 <= mi_rows && uc0 + 2 * cc + 2 <= mi_cols;
+        int       as16;
+        s32 += svt_ois_best16(ois, rr, cc, fits, lambda, &as16);
+        if (rr == r16 && cc == c16) as16_here = as16;
+    }
+    const svt_ois_block *b32 = &ois[svt_zorder4(c32, r32)];
+    const int            as32 = fit32 && b32->sad != SVT_OIS_NONE && svt_ois_cost(b32, lambda) <= s32;
+    int                  as8;
+    (void)svt_ois_best8(ois, r, c, lambda, &as8);
+    const svt_ois_block *b = as32 ? b32 : as16_here ? &ois[4 + svt_zorder4(c16, r16)] : &ois[20 + svt_zorder4(c, r)];
+    lf->skip = 0; lf->is_inter = 0; lf->filter_level = (uint8_t)filter_level;
+    lf->pad_[0] = 0; lf->pad_[1] = b->mode; lf->pad_[2] = b->uv_mode;
+    if (as32) { lf->sb_type = 9; lf->tx_size = 3; }
+    else if (as16_here) { lf->sb_type = 6; lf->tx_size = 2; }
+    else if (as8) { lf->sb_type = 3; lf->tx_size = 1; }
+    else { /* a unit of four 4x4 blocks: their modes in the nibbles of pad_[1] (blocks 0, 1) and pad_[0] (blocks 2, 3), the 8x8 record's chroma mode */
+        const svt_ois_block *b4 = &ois[84 + 4 * svt_zorder4(c, r)];
+        lf->sb_type = 0; lf->tx_size = 0;
+        lf->pad_[1] = (uint8_t)((b4[0].mode & 15) | (b4[1].mode & 15) << 4);
+        lf->pad_[0] = (uint8_t)((b4[2].mode & 15) | (b4[3].mode & 15) << 4);
+    }
 }
 
 #endif /* SVT_ENCDEC_CORE_H */

@@ -23,7 +23,8 @@
  *                                context (device-side waits, svt_hip_ctx_wait_marker); the reconstruction copies of get_recon run on
  *                                an OUTPUT context the same way (SVT_HIP_SINGLE_STREAM=1: everything on the main stream)
  *   intra pictures               coded by the intra encode pass (svt_hip_encdec_intra_device: wavefront prediction + transform, then
- *                                deblocking and border); the decision callback is asked for them too, the stand-in is 16x16 / DC; on a KEY
+ *                                deblocking and border); the decision callback is asked for them too, the stand-in is 16x16 / DC
+ *                                (SVT_HIP_INTRA_DECISION=search: the open-loop intra search + the grid built from its records); on a KEY
  *                                context of their own, beside the previous GOP's tail and the new GOP's motion estimation
  *   when a mini-GOP is complete  (or cut short by an intra refresh / the end of the stream: cut as the reference cuts it,
  *                                svt_hip_minigop_split) the caller's thread plans the group (structure, packets queued in decode order) and
@@ -168,6 +169,8 @@ typedef struct shim_dev {
     shim_slot       *slot;
     int64_t          accepted;       /* pictures this device has taken: ring position */
     void            *d_src_slab, *d_pred_slab, *d_q_slab, *d_dq_slab;
+    void            *d_ois;          /* SVT_HIP_INTRA_DECISION=search: the open-loop intra search records of the key frame being decided (n_sb *
+                                        SVT_OIS_PER_SB; written and read on the context of the intra pass, in stream order) */
     svt_encdec_work *work;
     shim_recon      *free_recon;     /* pinned buffers ready for re-use */
     /* The device's feeder: a thread that enqueues the planned groups of this device (motion estimation, statistics, the waves behind
@@ -213,6 +216,7 @@ typedef struct shim_state {
     size_t      pic_bytes, rec_bytes, coeffs;
     int         q_index, filter_level;
     uint32_t    md_lambda;
+    int         intra_search;          /* SVT_HIP_INTRA_DECISION=search: intra pictures no callback decided go through the open-loop intra search */
     svt_lf_thresh thr;
     svt_vp9_shim_md_callback md_cb;
     void       *md_user;
@@ -385,9 +389,9 @@ static void free_dev(shim_state *s, shim_dev *d) {
         free(d->slot);
         d->slot = NULL;
     }
-    void *v[4] = {d->d_src_slab, d->d_pred_slab, d->d_q_slab, d->d_dq_slab};
-    for (int k = 0; k < 4; k++) svt_hip_mem_free(d->ctx, v[k]);
-    d->d_src_slab = d->d_pred_slab = d->d_q_slab = d->d_dq_slab = NULL;
+    void *v[5] = {d->d_src_slab, d->d_pred_slab, d->d_q_slab, d->d_dq_slab, d->d_ois};
+    for (int k = 0; k < 5; k++) svt_hip_mem_free(d->ctx, v[k]);
+    d->d_src_slab = d->d_pred_slab = d->d_q_slab = d->d_dq_slab = d->d_ois = NULL;
     while (d->free_recon) { shim_recon *r = d->free_recon; d->free_recon = r->next; svt_hip_host_free(d->ctx, r->host); svt_hip_mem_free(d->ctx, r->d_tight); free(r); }
     if (d->work_key && d->work_key != d->work) svt_hip_encdec_work_destroy(d->ctx_key, d->work_key);
     d->work_key = NULL;
@@ -434,6 +438,7 @@ static int alloc_dev(shim_state *s, shim_dev *d) {
              (d->ctx_deep == d->ctx || svt_hip_encdec_work_create(d->ctx_deep, SHIM_WAVE_MAX, W, H, &d->work_deep) == SVT_HIP_OK);
     if (ok && d->ctx_key != d->ctx) ok = svt_hip_encdec_work_create(d->ctx_key, 1, W, H, &d->work_key) == SVT_HIP_OK;
     else d->work_key = d->work;
+    if (ok && s->intra_search) ok = svt_hip_mem_alloc(d->ctx, (size_t)s->n_sb * SVT_OIS_PER_SB * sizeof(svt_ois_block), &d->d_ois) == SVT_HIP_OK;
     for (int i = 0; ok && i < d->n_slots; i++) {
         shim_slot *t = &d->slot[i];
         t->number = -1;
@@ -507,6 +512,15 @@ EbErrorType eb_vp9_init_encoder(EbComponentType *h) {
         }
     }
     if (n == 0) { ord[0] = one ? atoi(one) : 0; n = 1; }
+    {   /* how intra pictures that no callback decides are decided: read per encoder (two encoders of a process may differ) */
+        const char *idm = getenv("SVT_HIP_INTRA_DECISION");
+        if (!idm || !*idm || !strcmp(idm, "dc")) s->intra_search = 0;
+        else if (!strcmp(idm, "search")) s->intra_search = 1;
+        else {
+            fprintf(stderr, "SvtVp9Enc: SVT_HIP_INTRA_DECISION=%s: expected \"dc\" or \"search\"\n", idm);
+            return EB_ErrorBadParameter;
+        }
+    }
     s->W = (int)s->cfg.source_width; s->H = (int)s->cfg.source_height;
     s->mi_rows = s->H >> 3; s->mi_cols = s->W >> 3;
     s->n_sb = svt_hip_sb_count(s->W, s->H);
@@ -909,7 +923,8 @@ static EbErrorType encode_wave(shim_state *s, shim_dev *d, const shim_job *const
 
 /* an intra picture (key frame / intra refresh): the intra encode pass on the GPU (svt_hip_encdec_intra_device: reference samples,
  * predictors, transform / quantisation / reconstruction in coding-dependency order, then deblocking and border).  The host's callback
- * decides its blocks and modes when it wants to (info->is_intra = 1, no ME results); otherwise the stand-in (16x16, DC). */
+ * decides its blocks and modes when it wants to (info->is_intra = 1, no ME results); otherwise the stand-in: 16x16 DC, or with
+ * SVT_HIP_INTRA_DECISION=search the open-loop intra search and the grid built from its records (decision_source 2). */
 static EbErrorType encode_intra(shim_state *s, shim_dev *d, shim_slot *t) {
     svt_encdec_flags fl;
     svt_hip_ctx *cx = d->ctx_key; /* (the main context without a key stream) */
@@ -936,7 +951,12 @@ static EbErrorType encode_intra(shim_state *s, shim_dev *d, shim_slot *t) {
         }
     }
     const double tk0 = s->profile > 1 ? now_s() : 0.0;
-    if (!decided) GPU_TRY(svt_hip_md_intra_default_device(cx, s->W, s->H, level, (svt_lf_mode_info *)t->d_lf_mi, s->mi_cols));
+    if (!decided && s->intra_search) {
+        const svt_yuv_planes src = tight_planes(s, t->d_src);
+        GPU_TRY(svt_hip_intra_search_device(cx, &src, s->W, s->H, (svt_ois_block *)d->d_ois));
+        GPU_TRY(svt_hip_md_intra_search_device(cx, (const svt_ois_block *)d->d_ois, s->W, s->H, s->md_lambda, level, (svt_lf_mode_info *)t->d_lf_mi, s->mi_cols));
+        t->info.decision_source = 2;
+    } else if (!decided) GPU_TRY(svt_hip_md_intra_default_device(cx, s->W, s->H, level, (svt_lf_mode_info *)t->d_lf_mi, s->mi_cols));
     const double tk1 = s->profile > 1 ? now_s() : 0.0;
     GPU_TRY(svt_hip_mem_set(cx, t->d_mc_mi, 0, (size_t)s->mi_rows * s->mi_cols * sizeof(svt_mc_mode_info))); /* no motion in an intra picture */
     const double tk2 = s->profile > 1 ? now_s() : 0.0;
