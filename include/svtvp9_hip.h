@@ -175,7 +175,7 @@ int32_t svt_hip_me_last_instance(const svt_hip_ctx *ctx);
  * widths that are multiples of 8; the launcher takes it where it buys a workgroup per CU: 160 KB per CU in granules of 1 280 bytes).  Negative: no such layout. */
 int32_t svt_hip_me_lds_bytes(const svt_me_params *p, int32_t compact);
 /* Deployment knob of the intra encode pass (svt_hip_encdec_intra_device, and the intra blocks of inter pictures) launched on ctx: at most n
- * one-wave workgroups (0 = the default: one per compute unit, the lowest latency for a key frame alone -- 6.5 ms at 2160p).  A pass that runs
+ * one-wave workgroups (0 = the default: two per compute unit, the lowest latency for a key frame alone).  A pass that runs
  * BESIDE other work of the device (a key frame of the next GOP beside the current one) leaves more of it to that work with fewer: every CU
  * that hosts one of its waves has registers for one motion-estimation workgroup less (128: 7.9 ms alone, +2 % for the pipelined step of
  * bench.py).  The environment's SVT_HIP_INTRA_WGS sets the process-wide default. */

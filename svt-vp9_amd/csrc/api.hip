@@ -136,28 +136,10 @@ extern "C" void svt_hip_ctx_destroy(svt_hip_ctx *c) {
     for (int i = 0; i < SVT_CTX_MARKERS; i++) if (c->mk_ev[i]) (void)hipEventDestroy(c->mk_ev[i]);
     if (c->ho_produced) (void)hipEventDestroy(c->ho_produced);
     if (c->ho_consumed) (void)hipEventDestroy(c->ho_consumed);
-    if (c->aux_fork) (void)hipEventDestroy(c->aux_fork);
-    for (int i = 0; i < 3; i++) {
-        if (c->aux[i]) { (void)hipStreamSynchronize(c->aux[i]); (void)hipStreamDestroy(c->aux[i]); }
-        if (c->aux_join[i]) (void)hipEventDestroy(c->aux_join[i]);
-    }
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
     free(c);
-}
-int svt_ctx_aux_init(svt_hip_ctx *c) {
-    if (c->aux_ready) return 0;
-    int prio = 0;
-    (void)hipStreamGetPriority(c->stream, &prio);
-    /* idempotent per resource: a call that failed half-way leaves its handles in place and the next call creates only what is missing */
-    if (!c->aux_fork && hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming) != hipSuccess) { c->aux_fork = nullptr; return -1; }
-    for (int i = 0; i < 3; i++) {
-        if (!c->aux[i] && hipStreamCreateWithPriority(&c->aux[i], hipStreamNonBlocking, prio) != hipSuccess) { c->aux[i] = nullptr; return -1; }
-        if (!c->aux_join[i] && hipEventCreateWithFlags(&c->aux_join[i], hipEventDisableTiming) != hipSuccess) { c->aux_join[i] = nullptr; return -1; }
-    }
-    c->aux_ready = 1;
-    return 0;
 }
 
 extern "C" int32_t svt_hip_ctx_synchronize(svt_hip_ctx *c) {

@@ -425,8 +425,8 @@ __global__ __launch_bounds__(128) void svt_lf_desc_kernel(const lf_pic_dev *__re
  *   wave 2  stages the NEXT SB meanwhile: waits for the SB row above, loads the 64 new columns + top halo and the edge
  *           descriptors (svt_lf_desc_kernel) into the other buffer;
  *   wave 3  writes the finished columns of the tile filtered in the previous step back and publishes the row's progress.
- * One workgroup barrier per SB; wave 2 lets its loads fly while wave 3 is still reading the buffer they will land in.  Tile rows 0-7 (top halo) and the SB's last 8 rows are seam rows (sc1 accesses). */
-template <bool early> /* seam rows are handed to the SB row below early, see step (c) (the default; <false>: with the tile's write-back) */
+ * One workgroup barrier per SB; wave 2 lets its loads fly while wave 3 is still reading the buffer they will land in.  Tile rows 0-7 (top halo) and the SB's last 8 rows are seam rows (sc1 accesses).
+ * Seam rows are handed to the SB row below early, see step (c). */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void svt_lf_kernel(const lf_pic_dev *__restrict__ pics, int n_pics,
                                                      uint32_t *__restrict__ ticket, int rows_per_pic, int prof) {
     __shared__ __align__(16) uint8_t ytile[2][YROWS * YS];
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const lf_geom g = lf_geometry(sb_row, sc, W, H);
         if (sb_row > 0) { /* wait for the SB row above to have handed over everything above this SB: its tile sc (columns up to 56)
                              and, early, the bottom rows of its last 8 columns, which (sb_row-1, sc+1)'s vertical pass finishes */
-            const uint32_t need = early ? (uint32_t)(sc + 1) : (uint32_t)(sc + 2 < sb_cols ? sc + 2 : sb_cols);
+            const uint32_t need = (uint32_t)(sc + 1);
             if (lane == 0)
                 while (__hip_atomic_load(LF_AS_GLOBAL(uint32_t, &P.progress[sb_row - 1]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) __builtin_amdgcn_s_sleep(1);
             LF_MARK(0, 128);
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             /* vertical edges: lane = sample row; horizontal edges: lane = sample column (LDS accesses of one wave are
              * ordered, no barrier between the two passes) */
             if (lane < g.vh) lf_line<true>(ytile[buf] + (8 + lane) * YS + 8, 1, 8, &s_desc[buf][2 * (lane >> 3) * 8], 1);
-            if (early && lane == 0) s_vdone[0] = sc; /* LDS accesses of one wave are ordered: the flag lands behind the pass's stores */
+            if (lane == 0) s_vdone[0] = sc; /* LDS accesses of one wave are ordered: the flag lands behind the pass's stores */
             LF_ROWTS(4, 0, sc == 1);
             LF_MARK(3, 0);
             while (s_halo < sc) __builtin_amdgcn_s_sleep(1); /* the rows above the SB have arrived */
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         } else if (wave == 1 && !P.y_only) {
             const int pl = lane >> 5, l5 = lane & 31;
             if (l5 < g.cvh) lf_line<true>(ctile[buf][pl] + (8 + l5) * CS + 8, 1, 4, &s_desc[buf][256 + 2 * (l5 >> 3) * 4], 1);
-            if (early && lane == 0) s_vdone[1] = sc;
+            if (lane == 0) s_vdone[1] = sc;
             while (s_halo < sc) __builtin_amdgcn_s_sleep(1);
             if (l5 < g.cvw) lf_line<false>(ctile[buf][pl] + 8 * CS + 8 + l5, CS, (nrows + 1) >> 1, &s_desc[buf][288 + 2 * (l5 >> 3)], 4);
             if (!last) {
@@ -563,15 +563,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
              * left-halo columns (the previous SB's last columns, which this SB's vertical pass finished) -- without their bottom 8
              * rows when an SB row below waits for them: those went out early, in the previous iteration's step (c), and the row
              * below may already have filtered and rewritten them. */
-            const bool below = early && sb_row + 1 < sb_rows;
-            if (!early) { /* throughput mode: one rectangle per plane (tile columns 8-hx .. 8+56, rows 8-hy .. 8+vh), nothing handed over early */
-                const int nxs = (last ? g.vw : 56) + g.hx, nxc = (last ? g.cvw : 24) + g.hx;
-                tile_io<11>(wide_y, false, P.planes.y, P.planes.y_stride, ytile[buf], YS, g.x0 - 8, g.y0 - 8, 8 - g.hx, 8 - g.hy, nxs, g.vh + g.hy, 8, 8 + g.vh - 8, lane, 64);
-                if (!P.y_only) {
-                    tile_io<3>(wide_c, false, P.planes.u, P.planes.uv_stride, ctile[buf][0], CS, g.cx0 - 8, g.cy0 - 8, 8 - g.hx, 8 - g.hy, nxc, g.cvh + g.hy, 8, 8 + g.cvh - 8, lane, 64);
-                    tile_io<3>(wide_c, false, P.planes.v, P.planes.uv_stride, ctile[buf][1], CS, g.cx0 - 8, g.cy0 - 8, 8 - g.hx, 8 - g.hy, nxc, g.cvh + g.hy, 8, 8 + g.cvh - 8, lane, 64);
-                }
-            } else {
+            const bool below = sb_row + 1 < sb_rows;
             const int  nown = last ? g.vw : 56, nownc = last ? g.cvw : 24, cut = below ? 8 : 0;
             tile_io<11>(wide_y, false, P.planes.y, P.planes.y_stride, ytile[buf], YS, g.x0 - 8, g.y0 - 8, 8, 8 - g.hy, nown, g.vh + g.hy, 8, 8 + g.vh - 8, lane, 64);
             if (g.hx) tile_io<2>(wide_y, false, P.planes.y, P.planes.y_stride, ytile[buf], YS, g.x0 - 8, g.y0 - 8, 0, 8 - g.hy, 8, g.vh + g.hy - cut, 8, 8 + g.vh - 8, lane, 64);
@@ -581,7 +573,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     tile_io<3>(wide_c, false, cp, P.planes.uv_stride, ctile[buf][pl], CS, g.cx0 - 8, g.cy0 - 8, 8, 8 - g.hy, nownc, g.cvh + g.hy, 8, 8 + g.cvh - 8, lane, 64);
                     if (g.hx) tile_io<1>(wide_c, false, cp, P.planes.uv_stride, ctile[buf][pl], CS, g.cx0 - 8, g.cy0 - 8, 0, 8 - g.hy, 8, g.cvh + g.hy - cut, 8, 8 + g.cvh - 8, lane, 64);
                 }
-            }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* the tile has left LDS: the buffer may be refilled */
             if (lane == 0) s_stored = sc;
@@ -657,14 +648,8 @@ static int32_t lf_launch(svt_hip_ctx *ctx, int n_pics, const svt_yuv_planes *d_r
      * the wavefront keeps busy"): 1.45 ms for 16 pictures -- the row-to-row lag (two SB steps of ~6.8 us) times 34 rows IS most of a
      * picture's time, and a workgroup that waits for its predecessor costs the launch nothing while one that has not started cannot take
      * its seam rows the moment they appear.  Inside the pipelined step the change is neutral (other kernels fill the device either way);
-     * one GOP at a time gains 6 %.  SVT_HIP_LF_ROWS / SVT_HIP_LF_EARLY override (experiments). */
-    static const int rows_env = getenv("SVT_HIP_LF_ROWS") ? atoi(getenv("SVT_HIP_LF_ROWS")) : 0;
-    const int rows_in_flight = rows_env > 0 ? rows_env : max_rows;
-    const int lf_wgs = n_pics * (max_rows < rows_in_flight ? max_rows : rows_in_flight);
-    static const int early_env = getenv("SVT_HIP_LF_EARLY") ? atoi(getenv("SVT_HIP_LF_EARLY")) : -1;
-    const int early = early_env >= 0 ? early_env : 1;
-    if (early) hipLaunchKernelGGL(svt_lf_kernel<true>, dim3(lf_wgs), dim3(256), 0, ctx->stream, (const lf_pic_dev *)d, n_pics, cnt, max_rows, want_prof ? 1 : 0);
-    else hipLaunchKernelGGL(svt_lf_kernel<false>, dim3(lf_wgs), dim3(256), 0, ctx->stream, (const lf_pic_dev *)d, n_pics, cnt, max_rows, want_prof ? 1 : 0);
+     * one GOP at a time gains 6 %. */
+    hipLaunchKernelGGL(svt_lf_kernel, dim3(n_pics * max_rows), dim3(256), 0, ctx->stream, (const lf_pic_dev *)d, n_pics, cnt, max_rows, want_prof ? 1 : 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
     if (want_prof) {

@@ -31,11 +31,6 @@ struct svt_hip_ctx {
     void       *ring_slab_host, *ring_slab_dev; /* SVT_CTX_RING x 64 KB, taken when the context is created (an entry used to take its buffers the
                                                    first time round the ring: 64 pairs of allocations inside the first pictures of a stream) */
     int         ring_pos;
-    /* helper streams for entry points whose kernels are independent of each other (the four transform sizes of a TQ batch):
-       forked from / joined into `stream` with events, so the call still behaves as one operation on the context's stream */
-    hipStream_t aux[3];
-    hipEvent_t  aux_fork, aux_join[3];
-    int         aux_ready;
     /* asynchronous uploads: the caller's rows are copied into a pinned buffer of this ring before the call returns, the device
        copy is ordered on the stream; a buffer is reused once the event behind its copy has completed */
     void       *up_host[SVT_CTX_UPLOAD_RING];
@@ -64,20 +59,12 @@ int     svt_ctx_stage(svt_hip_ctx *ctx, size_t bytes, void **host, void **dev);
 /* call after the last operation that reads the slot has been enqueued on ctx->stream */
 void    svt_ctx_stage_commit(svt_hip_ctx *ctx);
 void   *svt_ctx_slot(svt_hip_ctx *ctx, int slot, size_t bytes);
-/* creates the helper streams on first use (same priority as the context's stream); returns 0 on success */
-int     svt_ctx_aux_init(svt_hip_ctx *ctx);
 
 /* transform stage over device-built block lists (tq_kernel.hip; used by encdec.hip) */
 int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set,
                                    const svt_tq_block *d_blocks, const int32_t cap[4], const int32_t *d_off_cnt, const svt_quant_tables *d_qtabs,
                                    const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, uint64_t *d_dist,
                                    const uint32_t *d_pos, const void *d_geom, int geom_stride, const uint32_t *d_iscan_off, int sb_cols);
-
-/* the same over SB-ordered lists: one launch, workgroup = (picture, chunk of SVT_TQ_CHUNK_SBS SBs, size, part) (tq_kernel.hip: svt_tq_sb_kernel) */
-#define SVT_TQ_CHUNK_SBS 4
-int32_t svt_tq_launch_sb_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set, const svt_quant_tables *d_qtabs,
-                               const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, const uint32_t *d_pos, const void *d_geom, int geom_stride,
-                               const uint32_t *d_iscan_off, int sb_cols, const int32_t *d_seg, const int32_t *d_bases, int n_pics, int n_chunks, int seg_per_chunk);
 
 /* encode pass of an intra picture / the stand-in intra decision (intra_kernel.hip; used by encdec.hip).  d_sync: 2 + 3 * (number of
  * 16x16 luma cells) dwords of scratch */

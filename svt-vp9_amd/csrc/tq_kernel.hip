@@ -18,7 +18,6 @@
  */
 #include <hip/hip_runtime.h>
 #include "tq_core.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -134,7 +133,7 @@ __device__ __forceinline__ int rate_walk4(const int (&tok)[16], const int (&en)[
  * 8x8: they differ in the cast inside tx_fdct8 (vp9_dct.c:67-68), selected by the block's transform type.  The inverse
  * always runs all rows (the reference's reduced variants are shortcuts with identical results).  Memory instructions per
  * block are unchanged (a lane issues the N row loads its N lanes issued). */
-/* one 4x4 (8x8) block, whole, in the calling lane: the body of svt_tq_lane_kernel and of the 4x4 part of svt_tq_sb_kernel */
+/* one 4x4 (8x8) block, whole, in the calling lane: the body of svt_tq_lane_kernel */
 template <int N, bool RATE, bool DIST>
 __device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int blk, const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, uint8_t *__restrict__ recon,
                                               const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all, int16_t *__restrict__ qcoeff,
@@ -340,97 +339,14 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
   }
 }
 
-/* ---- the encode pass's transform stage as ONE launch over SB-ordered lists (round 6) ----
- * Four launches, one per transform size, each fetch the 128-byte lines of source and prediction they share with the others: an SB whose
- * 32x32 areas carry different transform sizes was read up to four times (2.08 GB per 16 pictures at 2160p against 1.0 GB of samples and
- * coefficients, profiles/r05_pmc_traffic.md) -- and at 0.54 ms for the four launches that is 3.8 TB/s: the stage was as close to the HBM
- * roof as to the issue roof.  Here the list is ordered [picture][chunk of SVT_TQ_CHUNK_SBS SBs][size][SB][unit][plane] (csrc/encdec.hip) and a
- * workgroup is (chunk, size, part): the SVT_TQ_SLOTS workgroups of a chunk are neighbours in dispatch order ON ONE XCD (workgroup w runs
- * on XCD w & 7), so a line one of them has fetched is in that XCD's L2 when the next one asks for it.  seg[] = the exclusive prefix of the
- * per-(picture, chunk, size, SB) counts inside a picture, bases[picture] (+ one closing entry) the pictures' first blocks.
- * 128 threads: four 32x32 blocks keep the transpose tiles at 16.9 KB (eight workgroups per CU at the 128 registers the 32x32 body needs). */
-constexpr int TQ_SB_NT = 128;
-__host__ __device__ constexpr int tq_sb_slots(int s) { return s == 0 ? 4 : s == 1 ? 4 : 2; } /* workgroups per (chunk, size) */
-__host__ __device__ constexpr int tq_sb_slots_range(int lo, int hi) { int n = 0; for (int s = lo; s <= hi; s++) n += tq_sb_slots(s); return n; }
-
-template <int N>
-__device__ __forceinline__ void tq_sb_groups(int32_t *tile_mem, const int first, const int count, const int part, const int nparts, const uint8_t *__restrict__ src,
-                                             const uint8_t *__restrict__ pred, const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all,
-                                             int16_t *__restrict__ qcoeff, int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out,
-                                             const uint8_t *const *__restrict__ recon_set, const tq_dev_count &dc) {
-    constexpr int BPW = TQ_SB_NT / N, LS = N + 1;
-    const int     lb = (int)threadIdx.x / N, i = (int)threadIdx.x % N;
-    int32_t      *t = tile_mem + lb * (N * LS);
-    for (int g = part; g * BPW < count; g += nparts) { /* (uniform) */
-        const int  b = g * BPW + lb;
-        const bool active = b < count;
-        const int  blk = first + (active ? b : 0);
-        svt_tq_block k;
-        const uint32_t pc = dc.pos[blk];
-        svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
-        uint32_t srow[N / 4], prow[N / 4];
-        {
-            const uint8_t *sp = src + k.src_off + (size_t)i * k.src_stride;
-            const uint8_t *pp = pred + k.pred_off + (size_t)i * k.pred_stride;
-            constexpr uintptr_t AM = N >= 16 ? 15 : N - 1;
-            _Pragma("unroll") for (int q = 0; q < N / 4; q++) { srow[q] = 0u; prow[q] = 0u; }
-            if (active) { row_load<N>(sp, ((uintptr_t)sp & AM) == 0, srow); row_load<N>(pp, ((uintptr_t)pp & AM) == 0, prow); }
-        }
-        tq_block_body<N, false, false>(k, active, i, t, srow, prow, qtabs, iscan_all, qcoeff, dqcoeff, eob_out + blk, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                       (uint8_t *)recon_set[(k.pad_[0] >> 4) & 7]);
-        tq_block_sync();
-    }
-}
-
-/* sizes S_LO .. S_HI of every chunk.  <0, 3>: everything in one launch (128 registers, 16.9 KB of LDS in EVERY workgroup, the 4x4 ones too);
- * <0, 2> + <3, 3>: the small sizes in a launch that needs 96 registers and 8.7 KB, the 32x32 blocks in one of their own -- see the launcher */
-template <int S_LO, int S_HI>
-__global__ __launch_bounds__(TQ_SB_NT) __attribute__((amdgpu_waves_per_eu(S_HI == 3 ? 4 : 5))) void svt_tq_sb_kernel(
-    const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all,
-    int16_t *__restrict__ qcoeff, int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out, const uint8_t *const *__restrict__ recon_set, tq_dev_count dc,
-    const int32_t *__restrict__ seg, const int32_t *__restrict__ bases, int n_chunks, int seg_per_chunk /* 4 * chunk SBs */, int n_items /* pictures x chunks */) {
-    constexpr int NMAX = 4 << S_HI, SLOTS = tq_sb_slots_range(S_LO, S_HI);
-    __shared__ int32_t tile_mem[S_HI == 0 ? 1 : (TQ_SB_NT / NMAX) * NMAX * (NMAX + 1)];
-    /* workgroup -> (item, slot): the slots of an item are consecutive on one XCD */
-    const int xcd = (int)(blockIdx.x & 7), local = (int)(blockIdx.x >> 3);
-    const int item = (local / SLOTS) * 8 + xcd, slot = local % SLOTS;
-    if (item >= n_items) return;
-    int s = S_LO, part = slot;
-    _Pragma("unroll") for (int q = S_LO; q < S_HI; q++) if (s == q && part >= tq_sb_slots(q)) { part -= tq_sb_slots(q); s = q + 1; }
-    const int nparts = tq_sb_slots(s);
-    const int pic = item / n_chunks, chunk = item - pic * n_chunks;
-    const int per_pic = n_chunks * seg_per_chunk, at = chunk * seg_per_chunk + s * (seg_per_chunk >> 2), nxt = at + (seg_per_chunk >> 2);
-    const int base = bases[pic];
-    const int first = base + seg[pic * per_pic + at];
-    const int last = nxt < per_pic ? base + seg[pic * per_pic + nxt] : bases[pic + 1];
-    const int count = last - first;
-    if (count <= 0) return;
-    if (S_LO == 0 && s == 0) { /* 4x4: a block per lane, no LDS, no barrier */
-        const tq_rate_args none = {nullptr, nullptr, nullptr};
-        for (int b = part * TQ_SB_NT + (int)threadIdx.x; b < count; b += nparts * TQ_SB_NT) {
-            const int      blk = first + b;
-            const uint32_t pc = dc.pos[blk];
-            svt_tq_block   k;
-            svt_tq_block_from_pos(pc, SVT_TX_4X4, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
-            tq_lane_block<4, false, false>(k, blk, src, pred, nullptr, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, nullptr, none, nullptr, nullptr, recon_set);
-        }
-    }
-    if (S_LO <= 1 && S_HI >= 1 && s == 1) tq_sb_groups<8>(tile_mem, first, count, part, nparts, src, pred, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, recon_set, dc);
-    if (S_LO <= 2 && S_HI >= 2 && s == 2) tq_sb_groups<16>(tile_mem, first, count, part, nparts, src, pred, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, recon_set, dc);
-    if (S_HI == 3 && s == 3) tq_sb_groups<32>(tile_mem, first, count, part, nparts, src, pred, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, recon_set, dc);
-}
-
 /* persistent grid: a multiple of 8 workgroups (one walk per XCD, tq_walk_of), at most `per_cu` per compute unit */
 int tq_grid(svt_hip_ctx *ctx, int ngroups, int per_cu) {
-    const int cus = ctx->cu_count;
-    static const int per_cu_env = getenv("SVT_HIP_TQ_PER_CU") ? atoi(getenv("SVT_HIP_TQ_PER_CU")) : 0;
-    if (per_cu_env > 0) per_cu = per_cu_env;
-    const int per_xcd = (ngroups + 7) / 8, cap = (cus * per_cu + 7) / 8;
+    const int per_xcd = (ngroups + 7) / 8, cap = (ctx->cu_count * per_cu + 7) / 8;
     return 8 * (per_xcd < cap ? per_xcd : cap);
 }
 
 template <int N, bool RATE, bool DIST = true>
-hipError_t launch_tq(svt_hip_ctx *ctx, hipStream_t st, const uint8_t *src, const uint8_t *pred, uint8_t *recon, const svt_tq_block *blocks, int n,
+hipError_t launch_tq(svt_hip_ctx *ctx, const uint8_t *src, const uint8_t *pred, uint8_t *recon, const svt_tq_block *blocks, int n,
                      const svt_quant_tables *q, const int16_t *iscan, int16_t *qc, int16_t *dqc, uint16_t *eob, uint64_t *dist, tq_rate_args ra,
                      const uint8_t *const *recon_set, tq_dev_count dc = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0}) {
     if (n <= 0) return hipSuccess;
@@ -438,12 +354,12 @@ hipError_t launch_tq(svt_hip_ctx *ctx, hipStream_t st, const uint8_t *src, const
      * intermediate live in one lane; 87 spills when held to 128) -- two waves per SIMD, and each displaces two ME waves:
      * the overlapped step went from 3.27 to 3.77 ms with it, so 8x8 stays on the N-lanes-per-block kernel */
     if constexpr (N == 4) {
-        hipLaunchKernelGGL((svt_tq_lane_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + 255) / 256, 6)), dim3(256), 0, st, src, pred, recon, blocks, n, q,
+        hipLaunchKernelGGL((svt_tq_lane_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + 255) / 256, 6)), dim3(256), 0, ctx->stream, src, pred, recon, blocks, n, q,
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     } else {
         constexpr int NT = tq_threads<N, RATE>(), BPW = NT / N;
-        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, 6)), dim3(NT), 0, st, src, pred, recon, blocks, n, q,
+        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, 6)), dim3(NT), 0, ctx->stream, src, pred, recon, blocks, n, q,
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     }
@@ -464,32 +380,16 @@ int32_t tq_launch_all(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_p
         d_set = (const uint8_t *const *)d;
     }
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-    /* The four size groups are independent of each other; SVT_HIP_TQ_FORK=1 launches each on a stream of its own (forked from
-     * and joined into the context's stream).  Measured: slower -- 1.59 instead of 1.39 ms per mini-GOP for the four launches
-     * alone, no change inside the pipeline: kernels that share compute units take longer in sum than one after the other (every
-     * pairing of the stages shows it), so the default keeps them in sequence. */
-    static const bool want_fork = getenv("SVT_HIP_TQ_FORK") != nullptr;
-    const bool        fork = want_fork && svt_ctx_aux_init(ctx) == 0;
-    if (fork) {
-        HIP_TRY(hipEventRecord(ctx->aux_fork, ctx->stream));
-        for (int i = 0; i < 3; i++) HIP_TRY(hipStreamWaitEvent(ctx->aux[i], ctx->aux_fork, 0));
-    }
     int        off = 0;
     hipError_t rc = hipSuccess;
     auto at = [&](int o) { tq_rate_args r = ra; if (r.bits) r.bits += o; return r; };
-    auto on = [&](int i) { return fork && i > 0 ? ctx->aux[i - 1] : ctx->stream; };
-    rc = launch_tq<4, RATE>(ctx, on(0), d_src, d_pred, d_recon, d_blocks + off, size_count[0], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
+    rc = launch_tq<4, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[0], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
     off += size_count[0];
-    if (rc == hipSuccess) rc = launch_tq<8, RATE>(ctx, on(1), d_src, d_pred, d_recon, d_blocks + off, size_count[1], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
+    if (rc == hipSuccess) rc = launch_tq<8, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[1], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
     off += size_count[1];
-    if (rc == hipSuccess) rc = launch_tq<16, RATE>(ctx, on(2), d_src, d_pred, d_recon, d_blocks + off, size_count[2], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
+    if (rc == hipSuccess) rc = launch_tq<16, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[2], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
     off += size_count[2];
-    if (rc == hipSuccess) rc = launch_tq<32, RATE>(ctx, on(3), d_src, d_pred, d_recon, d_blocks + off, size_count[3], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
-    if (fork)
-        for (int i = 0; i < 3; i++) {
-            (void)hipEventRecord(ctx->aux_join[i], ctx->aux[i]);
-            (void)hipStreamWaitEvent(ctx->stream, ctx->aux_join[i], 0);
-        }
+    if (rc == hipSuccess) rc = launch_tq<32, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[3], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
     (void)hipEventRecord(ctx->ev_stop, ctx->stream); /* also on a failed launch: ev_start is already in the stream */
     if (recon_set) svt_ctx_stage_commit(ctx);
     if (rc != hipSuccess) return svt_set_hip_error(rc, __FILE__, __LINE__);
@@ -514,7 +414,7 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
     const uint8_t *const *d_set = (const uint8_t *const *)d;
     const tq_rate_args none = {nullptr, nullptr, nullptr};
     hipError_t rc = hipSuccess;
-#define TQ_DEV(N, S, D) launch_tq<N, false, D>(ctx, ctx->stream, d_src, d_pred, nullptr, d_blocks, cap[S], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob, d_dist, none, d_set, tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols})
+#define TQ_DEV(N, S, D) launch_tq<N, false, D>(ctx, d_src, d_pred, nullptr, d_blocks, cap[S], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob, d_dist, none, d_set, tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols})
     if (d_dist) { /* with the coefficient-domain distortion pair */
         rc = TQ_DEV(4, 0, true);
         if (rc == hipSuccess) rc = TQ_DEV(8, 1, true);
@@ -527,34 +427,6 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
         if (rc == hipSuccess) rc = TQ_DEV(32, 3, false);
     }
 #undef TQ_DEV
-    svt_ctx_stage_commit(ctx);
-    if (rc != hipSuccess) return svt_set_hip_error(rc, __FILE__, __LINE__);
-    return SVT_HIP_OK;
-}
-
-/* The same stage over the SB-ordered device lists (csrc/encdec.hip): ONE launch, workgroup = (picture, chunk, size, part).  d_seg: per picture
- * n_chunks x seg_per_chunk exclusive prefixes, d_bases: n_pics + 1 first blocks.  No distortion, no rate (the encode pass).  Internal. */
-int32_t svt_tq_launch_sb_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set, const svt_quant_tables *d_qtabs,
-                               const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, const uint32_t *d_pos, const void *d_geom, int geom_stride,
-                               const uint32_t *d_iscan_off, int sb_cols, const int32_t *d_seg, const int32_t *d_bases, int n_pics, int n_chunks, int seg_per_chunk) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    void *h = nullptr, *d = nullptr;
-    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
-    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr;
-    HIP_TRY(hipMemcpyAsync(d, h, 8 * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    const int n_items = n_pics * n_chunks, groups8 = (n_items + 7) / 8;
-    const tq_dev_count dc{nullptr, 0, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols};
-    /* SVT_HIP_TQ_SB_SPLIT: 0 (default) = everything in one launch; 1 = sizes 4x4 .. 16x16 in one launch (96 registers, 8.7 KB of LDS), the 32x32
-     * blocks in a second; 2 = 4x4 + 8x8 | 16x16 + 32x32.  Measured (tools/r06_tq_ab.sh, tools/r06_tq_traffic.sh): traffic 1.50 / 1.73 GB per 16
-     * pictures for 0 / 1, step 10.5 / 10.4 / 10.65 ms for 0 / 1 / 2 against 10.2 ms with the size-grouped lists. */
-    static const int split = getenv("SVT_HIP_TQ_SB_SPLIT") ? atoi(getenv("SVT_HIP_TQ_SB_SPLIT")) : 0;
-#define TQ_SB_LAUNCH(LO, HI) hipLaunchKernelGGL((svt_tq_sb_kernel<LO, HI>), dim3(groups8 * tq_sb_slots_range(LO, HI) * 8), dim3(TQ_SB_NT), 0, ctx->stream, d_src, d_pred, d_qtabs, d_iscan, \
-                                                d_qcoeff, d_dqcoeff, d_eob, (const uint8_t *const *)d, dc, d_seg, d_bases, n_chunks, seg_per_chunk, n_items)
-    if (split == 0) TQ_SB_LAUNCH(0, 3);
-    else if (split == 2) { TQ_SB_LAUNCH(0, 1); TQ_SB_LAUNCH(2, 3); }
-    else { TQ_SB_LAUNCH(0, 2); TQ_SB_LAUNCH(3, 3); }
-#undef TQ_SB_LAUNCH
-    const hipError_t rc = hipGetLastError();
     svt_ctx_stage_commit(ctx);
     if (rc != hipSuccess) return svt_set_hip_error(rc, __FILE__, __LINE__);
     return SVT_HIP_OK;
