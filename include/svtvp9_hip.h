@@ -380,6 +380,61 @@ int32_t svt_hip_pa_prepare_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const 
  * Codec/EbMotionEstimationContext.h:45-131).  SBs at the right/bottom border read the replicated padding. */
 int32_t svt_hip_pa_mean_variance_device(svt_hip_ctx *ctx, const svt_plane *full, uint8_t *d_mean, uint16_t *d_var);
 
+/* Noise detection = picture_pre_processing_operations (Codec/EbPictureAnalysisProcess.c:4191-4232) without the denoiser, which the
+ * reference never reaches (enable_denoise_src_flag is false for tune 1, 2 and compiled out for tune 0 by TURN_OFF_PRE_PROCESSING). */
+#define SVT_PA_NOISE_FULL 0    /* detect_input_picture_noise (:3512-3619) on the full picture, 64x64 variance per complete SB */
+#define SVT_PA_NOISE_HALF 1    /* sub_sample_detect_noise (:3930-4055) on the 1/16 picture, 16x16 variance per SB */
+#define SVT_PA_NOISE_QUARTER 2 /* quarter_sample_detect_noise (:3809-3928) on the 1/4 picture, 32x32 variance per SB */
+
+typedef struct svt_pa_noise_params {
+    int32_t method;             /* SVT_PA_NOISE_* (not the reference's NOISE_DETECT_* numbering) */
+    int32_t noise_detection_th; /* picture_control_set_ptr->noise_detection_th, 0 or 1 */
+    int32_t luma_height;        /* sequence_control_set_ptr->luma_height: selects the class ladder's offset */
+} svt_pa_noise_params;
+
+typedef struct svt_pa_noise_result {
+    uint32_t pic_noise_class;        /* PIC_NOISE_CLASS_1, 2, 3, 3_1 = 1, 2, 3, 4 (Codec/EbDefinitions.h:860-871) */
+    uint32_t sb_count;               /* tot_sb_count: the SBs the loop visited */
+    uint64_t pic_noise_variance_sum; /* sum of (noiseBlkVar >> 16); pic_noise_variance_float = sum / (double)sb_count */
+} svt_pa_noise_result;
+
+/* The noise fields of eb_vp9_signal_derivation_pre_analysis_sq / _oq / _vmaf (Codec/EbResourceCoordinationProcess.c:291-440) for
+ * tune 0 / 1 / 2, enc_mode 0..12 and the picture size (through the input-resolution class of the helper above). */
+int32_t svt_hip_pa_noise_params_derive(svt_pa_noise_params *p, int32_t tune, int32_t enc_mode, int32_t pic_width, int32_t pic_height);
+
+/* For each picture of the batch: the weak luma filter (N + W + 4C + E + S) / 8 (get_filtered_types type 0, :1403-1412, as
+ * eb_vp9_noise_extract_luma_weak applies it, :1653-1706: picture-border samples are copied and their noise is 0), the difference
+ * clip(in - filtered), and the block variances of both, on pics[i].full / .sixteenth / .quarter by params->method.  Written:
+ *   d_sb_flat_noise[i][sb] (ceil(W/64) * ceil(H/64) bytes of the full picture, every one of them: 0 for SBs the reference's loop
+ *   does not visit) and d_result[i].  The decimated forms visit only the whole 64x64 blocks of the decimated picture and take the
+ *   noise variance of all SB rows of such a block from its first SB row, as the reference does.
+ * d_denoised / d_noise are both NULL, or both arrays of n_pics dense planes of the analysed picture (stride = its width): they
+ * receive the filtered and the noise samples of the area the reference's loop filters (all of the picture for the full form, the
+ * whole 64x64 blocks for the others) and exist so that a test can compare with the reference's own filter.  When they are NULL
+ * those samples never leave the registers.  The pointer arrays are host memory, what they point to is device memory. */
+int32_t svt_hip_pa_noise_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture *pics, const svt_pa_noise_params *params,
+                                      uint8_t *const *d_sb_flat_noise, svt_pa_noise_result *d_result, uint8_t *const *d_denoised,
+                                      uint8_t *const *d_noise);
+
+/* Intensity histograms and averages = sub_sample_luma_generate_pixel_intensity_histogram_bins (:4237-4312) on pics[i].sixteenth,
+ * its chroma twin (:4314-4432) on cb[i] / cr[i] (the source chroma planes, (W/2) x (H/2) of pics[i].full's W x H, every 4th row
+ * and column; their sample (0,0) is the one under luma (0,0)) and calculate_input_average_intensity (:4839-4886).
+ *   d_hist[i]       uint32 [regions_w][regions_h][3][256]  (1 + count) << 4
+ *   d_avg_region[i] uint8  [regions_w][regions_h][3]
+ *   d_avg[i]        uint8  [3]; with scd_mode 0 only [0] is written, from the 8x8 sub-sampled means of the W x H bytes at
+ *                   pics[i].full.buf (the reference indexes buffer_y without the origin there, :4857-4860)
+ * The last region in each direction takes the remainder of the division. */
+int32_t svt_hip_pa_histogram_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture *pics, const svt_plane *cb,
+                                          const svt_plane *cr, int32_t regions_w, int32_t regions_h, int32_t scd_mode,
+                                          uint32_t *const *d_hist, uint8_t *const *d_avg_region, uint8_t *const *d_avg);
+
+/* cb_mean / cr_mean [sb][21] = compute_chroma_block_mean (:1828-2109) for complete SBs of a width x height luma picture, zero for
+ * the others (zero_out_chroma_block_mean): index 0 = 64x64, 1-4 = 32x32, 5-20 = 16x16 luma blocks in raster order, from
+ * eb_vp9_compute_sub_mean8x8_sse2_intrin sums of the 8x8 chroma blocks.  The 64x64 entry is (m32[0] + m32[1] + 2 * m32[3]) >> 2,
+ * as the reference writes it (:2010-2015). */
+int32_t svt_hip_pa_chroma_mean_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_plane *cb, const svt_plane *cr, int32_t width,
+                                            int32_t height, uint8_t *const *d_cb_mean, uint8_t *const *d_cr_mean);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* Transform / quantisation                                                                           */
 /* ------------------------------------------------------------------------------------------------ */

@@ -173,6 +173,7 @@ EXPORTS = [
     "svt_hip_mem_download_2d_async", "svt_hip_mem_copy_2d_device", "svt_hip_encdec_work_set_stage_hook", "svt_hip_me_params_same_launch", "svt_hip_me_kernel_instance", "svt_hip_ctx_set_intra_workgroups", "svt_hip_ctx_warm", "svt_hip_ctx_warm_scratch", "svt_hip_lf_reserve",
     "svt_hip_me_last_instance", "svt_hip_me_lds_bytes", "svt_hip_vp9_layer_qindex", "svt_hip_mem_upload_2d_direct", "svt_hip_mem_upload_wait", "svt_hip_host_unregister_all", "svt_hip_host_registry_retain", "svt_hip_host_registry_release",
     "svt_hip_intra_search_device", "svt_hip_md_intra_search_device", "svt_hip_md_intra_search_picture",
+    "svt_hip_pa_noise_params_derive", "svt_hip_pa_noise_batch_device", "svt_hip_pa_histogram_batch_device", "svt_hip_pa_chroma_mean_batch_device",
 ]
 
 _lib = None
@@ -216,6 +217,21 @@ class MePictureConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("pic_width", "pic_height", "enc_mode", "tune", "frame_rate", "num_ref_lists",
                                          "temporal_layer_index", "hierarchical_levels", "is_used_as_reference", "same_ref_poc",
                                          "rate_control_mode")]
+
+
+class PaNoiseParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("noise_detection_th", C.c_int32), ("luma_height", C.c_int32)]
+
+
+PA_NOISE_FULL, PA_NOISE_HALF, PA_NOISE_QUARTER = 0, 1, 2
+# svt_pa_noise_result
+PA_NOISE_RESULT_DTYPE = np.dtype([("pic_noise_class", np.uint32), ("sb_count", np.uint32), ("pic_noise_variance_sum", np.uint64)])
+
+
+def pa_noise_params_derive(tune, enc_mode, width, height):
+    p = PaNoiseParams()
+    check(load().svt_hip_pa_noise_params_derive(C.byref(p), tune, enc_mode, width, height))
+    return p
 
 
 def me_params_derive(**kw):

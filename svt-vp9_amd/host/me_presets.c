@@ -139,3 +139,23 @@ int32_t svt_hip_me_params_same_launch(const svt_me_params *a, const svt_me_param
 #undef EQ
 #undef EQ2
 }
+
+/* The noise-detection signals of the same three pre-analysis derivations (Codec/EbResourceCoordinationProcess.c:297-328 SQ,
+ * :365-393 OQ, :433-437 VMAF).  method uses SVT_PA_NOISE_*, not the reference's NOISE_DETECT_* numbering. */
+int32_t svt_hip_pa_noise_params_derive(svt_pa_noise_params *p, int32_t tune, int32_t enc_mode, int32_t pic_width, int32_t pic_height) {
+    if (!p || tune < 0 || tune > 2 || enc_mode < 0 || enc_mode > 12 || pic_width < 1 || pic_height < 1) return SVT_HIP_ERR_BAD_PARAMETER;
+    const int res = svt_hip_input_resolution(pic_width, pic_height);
+    p->luma_height = pic_height;
+    if (tune == 2) {
+        p->method             = SVT_PA_NOISE_QUARTER;
+        p->noise_detection_th = 1;
+        return SVT_HIP_OK;
+    }
+    const int full_up_to = tune == 0 ? 8 : 3; /* ENC_MODE_8 (SQ) / ENC_MODE_3 (OQ) */
+    if (res == 3) p->method = enc_mode <= full_up_to ? SVT_PA_NOISE_FULL : SVT_PA_NOISE_HALF;
+    else if (res == 2) p->method = enc_mode <= full_up_to ? SVT_PA_NOISE_FULL : SVT_PA_NOISE_QUARTER;
+    else p->method = SVT_PA_NOISE_FULL;
+    if (tune == 0) p->noise_detection_th = enc_mode <= 8 ? 0 : 1;
+    else p->noise_detection_th = enc_mode <= 3 ? 0 : enc_mode <= 8 ? (res <= 2 ? 1 : 0) : 1;
+    return SVT_HIP_OK;
+}
