@@ -1875,7 +1875,10 @@ SVT_DEV void me_qsad_row4(const uint32_t *wr, const uint32_t *br, uint64_t *acc)
     *acc = a;
 }
 SVT_DEV void me_qsad_block(const uint8_t *blk, int bstride, int nd, int bh, const uint8_t *win, int wstride, int mul, uint32_t a[4]) {
-    const int flush = nd <= 4 ? 16 : nd <= 8 ? 8 : 4; /* rows whose sums (4*nd*255 each) still fit 16 bits */
+    /* rows whose sums (4*nd*255 each) still fit 16 bits.  The even / odd accumulators below hold flush/2 rows each, so the bound has a factor
+     * of two of slack (twice the rows still fit); four times does not: 16 rows of 64 samples carry into the neighbouring field, at the ceiling
+     * only (tests/test_me_ceiling.py) */
+    const int flush = nd <= 4 ? 16 : nd <= 8 ? 8 : 4;
     a[0] = a[1] = a[2] = a[3] = 0;
     for (int j0 = 0; j0 < bh; j0 += flush) {
         uint64_t  acc0 = 0, acc1 = 0; /* even / odd rows of the group: each holds at most flush/2 rows */

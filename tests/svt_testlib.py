@@ -132,6 +132,22 @@ def oracle_me_picture(cur, ref0, ref1, params, sb_begin=0, sb_end=-1):
     return res, rcme
 
 
+def oracle_me_picture_per_sb(cur, ref0, ref1, params, sb_begin=0, sb_end=-1):
+    """svt_oracle_me_picture with one call per SB: the yardstick with the product's model, "no state crosses an SB".  A whole-picture
+    run carries the reference's MeContext over from SB to SB, and where a list's best 64x64 SAD stays at its initial value
+    64 * 64 * 255 (no position is strictly better) it returns the vector of the SB before; a fresh context returns (0, 0) there,
+    as the kernel does ("The 64x64 vector at exactly MAX_SAD_VALUE")."""
+    nsb = n_sb(cur.luma.shape[1], cur.luma.shape[0])
+    if sb_end < 0 or sb_end > nsb:
+        sb_end = nsb
+    res = np.zeros((nsb, 85), dtype=B.ME_RESULT_DTYPE)
+    rcme = np.zeros(nsb, dtype=np.uint32)
+    for sb in range(sb_begin, sb_end):
+        r, c = oracle_me_picture(cur, ref0, ref1, params, sb, sb + 1)
+        res[sb], rcme[sb] = r[sb], c[sb]
+    return res, rcme
+
+
 def oracle_me_picture_mt(cur, ref0, ref1, params, threads=None):
     """svt_oracle_me_picture over the whole picture, SB ranges spread over host threads (ctypes drops the GIL; an SB's result
     depends on nothing outside the SB, and the oracle keeps its working state per call)."""
@@ -719,6 +735,27 @@ def make_sad_loop_case(seed, n_jobs=48):
         src[:bh, 64 * j:64 * j + bw] = blk
         jobs[j] = (64 * j, y0 * 1024 + x0, 4096, 2048, 1024, bw, bh, sw, sh)
     return dict(src=src, ref=ref, jobs=jobs)
+
+
+def make_sad_loop_ceiling_case():
+    """The same three block shapes at the ceiling of their sums: a block of 255 over a window of 0 (16x8: 32 640, 32x16: 130 560, 64x32: 522 240
+    at every position -- the first in raster order wins), and the same with one exact match planted LAST in raster order (every position before
+    it lies at or near the ceiling), over the largest level-0 window (224 x 112) and a 1 x 1 window.  Every job has its own 320 columns of the
+    reference plane.  Returns the case and the expected (best_sad, x, y) per job."""
+    shapes = [(bw, bh, sw, sh, plant) for (bw, bh) in ((16, 8), (32, 16), (64, 32)) for (sw, sh) in ((224, 112), (1, 1)) for plant in (0, 1)]
+    src = np.zeros((64, 64 * len(shapes)), np.uint8)
+    ref = np.zeros((200, 320 * len(shapes)), np.uint8)
+    jobs = np.zeros(len(shapes), dtype=B.SAD_LOOP_JOB_DTYPE)
+    want = np.zeros((len(shapes), 3), np.int64)
+    W = ref.shape[1]
+    for j, (bw, bh, sw, sh, plant) in enumerate(shapes):
+        x0, y0 = 320 * j + 8, 4
+        src[:bh, 64 * j:64 * j + bw] = 255
+        if plant:
+            ref[y0 + sh - 1:y0 + sh - 1 + 2 * bh:2, x0 + sw - 1:x0 + sw - 1 + bw] = 255
+        jobs[j] = (64 * j, y0 * W + x0, src.shape[1], 2 * W, W, bw, bh, sw, sh)
+        want[j] = (0, sw - 1, sh - 1) if plant else (bw * bh * 255, 0, 0)
+    return dict(src=src, ref=ref, jobs=jobs), want
 
 
 def _sad_loop_run(fn, case, is_ref):

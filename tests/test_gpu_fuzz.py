@@ -16,6 +16,13 @@ def test_me_random_sweep(seed):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_me_ceiling_sweep():
+    """tools/me_fuzz.py ceil: per SB a random kind of tests/me_ceiling.py (sums at the ceiling of the packed fields) or a smooth clip, every
+    preset and C5, HIP == the oracle run per SB"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "me_fuzz.py"), "40", "303", "ceil"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_lf_random_sweep():
     """tools/lf_fuzz.py: random sizes, masks, levels, sharpness 0..7, noisy and smooth (flat-filter) content"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lf_fuzz.py"), "60", "5"], capture_output=True, text=True, timeout=900)

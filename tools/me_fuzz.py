@@ -1,8 +1,12 @@
 """Randomised parity sweep of the ME kernel against the oracle (GPU): random picture sizes (incl. partial SBs), content kinds
-(smooth motion, noise, flat / tie-heavy, blocky), presets, list counts and temporal layers.  tools/me_fuzz.py [cases] [seed] [fast]
+(smooth motion, noise, flat / tie-heavy, blocky), presets, list counts and temporal layers.  tools/me_fuzz.py [cases] [seed] [fast|c5|ceil]
 `fast`: the 2160p enc-mode-8 preset on pictures of whole SB columns only (csrc/me_fast.h's driver; the run checks that it served).
 `c5`: the 2160p enc-mode-3 preset (64x64 area, SSD search, three HME levels) with mutated search areas (multiples of 8: the compact LDS layout
-with its second launch, csrc/me_layout.h; others: the plain one), 8x8 modes and metrics -- on small pictures most SBs meet clipped areas."""
+with its second launch, csrc/me_layout.h; others: the plain one), 8x8 modes and metrics -- on small pictures most SBs meet clipped areas.
+`ceil`: content from tests/me_ceiling.py, per 64x64 SB a random kind (0 / 255 pictures whose sums sit at the ceiling of the kernels' packed fields)
+or a smooth clip, so that ceiling SBs and ordinary SBs are neighbours; every preset and C5; compared with the oracle run one call per SB (where a
+list's best 64x64 SAD stays at 64 * 64 * 255 a whole-picture run returns the vector of the SB before).  The other modes' random
+stream is what it was."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -14,6 +18,8 @@ n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 fast = len(sys.argv) > 3 and sys.argv[3] == "fast"
 c5 = len(sys.argv) > 3 and sys.argv[3] == "c5"
+ceil = len(sys.argv) > 3 and sys.argv[3] == "ceil"
+if ceil: import me_ceiling as MK   # only this mode needs the generator: the other modes run on their own
 lib.svt_hip_me_last_instance.argtypes = [C.c_void_p]
 
 def content(kind, w, h):
@@ -40,8 +46,9 @@ for i in range(n_cases):
     kind = int(rng.integers(0, 5)); name = names[int(rng.integers(len(names)))]
     nl = int(rng.integers(1, 3)); tl = int(rng.integers(0, 5))
     if fast: w, name = 64 * int(rng.integers(2, 8)), "c3_2160p_m8"
-    pics = [T.PaPic(f) for f in content(kind, w, h)]
+    pics = [T.PaPic(f) for f in (MK.mixed_content(w, h, rng) if ceil else content(kind, w, h))]
     p = MC.preset(name, nl, tl)
+    if ceil and rng.integers(0, 4) == 0: p, name = MC.preset_c5(nl, tl & 3), "c5"
     if c5:
         p = MC.preset_c5(nl, tl & 3)
         p.search_area_width, p.search_area_height = [(64, 64), (64, 64), (48, 40), (56, 64), (64, 24), (40, 56), (61, 33), (24, 64)][int(rng.integers(8))]
@@ -50,7 +57,7 @@ for i in range(n_cases):
         name = "c5 %dx%d cu8=%d method=%d" % (p.search_area_width, p.search_area_height, p.cu8x8_mode, p.fractional_search_method)
     if nl == 2 and rng.integers(0, 4) == 0: p.same_ref_poc = 1
     r1 = pics[2] if nl == 2 else None
-    o, _ = T.oracle_me_picture(pics[1], pics[0], r1, p)
+    o, _ = (T.oracle_me_picture_per_sb if ceil else T.oracle_me_picture)(pics[1], pics[0], r1, p)
     g = hip(pics[1], pics[0], r1, p)
     if fast and not os.environ.get("SVT_HIP_ME_NOFAST"): assert lib.svt_hip_me_last_instance(ctx) == 101, lib.svt_hip_me_last_instance(ctx)
     m = T.me_results_equal(o, g, nl)
