@@ -19,14 +19,15 @@
  *     32-bit LDS min per wave; the window stride of the common 64-wide area is a compile-time constant (immediate offsets);
  *   - su_pel_enable: the 4 + 16 motion vectors / SADs sit in two DPP rows of wave 0; the decision is taken there and
  *     published as two bits.
- * Everything else (full-pel, interpolation, refinement, output) is shared with me_core.h.  Device only: the CPU emulation
- * (tests/emu) runs the general driver, and the -m gpu parity tests against the oracle pin this one.
+ * Everything else is shared with the general driver: full-pel (me_fullpel.h), interpolation and refinement (me_subpel.h), output
+ * (me_core.h); the marks (FME_MARK) are me_prof.h's.  Device only: the CPU emulation (tests/emu) runs the general driver, and the
+ * -m gpu parity tests against the oracle pin this one.
  */
 #ifndef SVT_ME_FAST_H
 #define SVT_ME_FAST_H
 #include "me_core.h"
 
-#ifndef SVT_HOST_EMU
+#ifndef SVT_HOST_EMU /* device only, the whole file: the emulation runs the general driver me_sb_run; pinned by tests/test_gpu_me_ceiling.py and tests/test_gpu_reference_contact.py */
 
 /* the presets this driver serves (compile-time property of a specialised instance) */
 constexpr bool me_fast_params_ok(uint8_t hme, uint8_t l0, uint8_t l1, uint8_t l2, uint8_t single, uint8_t method, uint8_t model, uint8_t f64,
@@ -36,13 +37,6 @@ constexpr bool me_fast_params_ok(uint8_t hme, uint8_t l0, uint8_t l1, uint8_t l2
 
 /* sums of the centre tests: slot s = 2 * list + (0: test_search_area_bounds, 1: check_zero_zero_center), five dwords each; they
  * live in the bytes of hme_sad (the general driver's per-level results: unused here) */
-#if defined(ME_ASM_MARKS) /* static instruction counts (tools/me_static_counts.py): a comment in the assembly at every mark */
-#define FME_MARK(i) __asm__ volatile("; @MARK %0" ::"n"(i))
-#elif defined(ME_FINE_PROF) /* dynamic counts and times per phase (tools/me_phase_profile.sh): the kernel ends at mark g_me_stop_after of list 0 */
-#define FME_MARK(i) do { if (g_me_stop_after == (i)) return; } while (0)
-#else
-#define FME_MARK(i) ((void)0)
-#endif
 #define FME_ACC(st, s) ((uint32_t *)(st)->hme_sad + 5 * (s))
 /* HME arg-min key (sad << 16 | y << 8 | x) of list l: in the bytes of hme_keys */
 #define FME_HKEY(st, l) ((uint32_t *)(st)->hme_keys + (l))
@@ -335,7 +329,7 @@ SVT_DEV void fme_fetch16(const uint8_t *lds, uint32_t a, uint32_t v[4]) {
 SVT_DEV uint32_t fme_src_at(uint32_t code, uint32_t bp, uint32_t bf) { return ((code & 0x8000u) ? bf : bp) + (code & 0x7fffu); }
 
 /* ---- half- and quarter-pel refinement of the 32x32 and 16x16 PUs, both decisions and every level of the bi-prediction in ONE
- * phase: the same lane roles and the same arithmetic as ph_subpel_fast (me_core.h) -- waves 0-1 the four 32x32 PUs (32 lanes each:
+ * phase: the same lane roles and the same arithmetic as ph_subpel_fast (me_subpel.h) -- waves 0-1 the four 32x32 PUs (32 lanes each:
  * 16 subsampled rows x 2 halves), waves 2-3 the sixteen 16x16 PUs (8 lanes each), a lane owns 16 samples of one row, DPP sums inside
  * the PU, decisions in the PU's last lane, published through LDS -- with the addressing taken out of the instruction stream:
  *   - the eight half-pel candidates lie at compile-time distances from the lane's position in plane B and fall into two alignment

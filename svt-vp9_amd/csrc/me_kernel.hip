@@ -1,6 +1,6 @@
 /*
  * me_kernel.hip -- gfx950 kernels for the motion-estimation path and their launchers.
- * The per-SB algorithm lives in me_core.h (shared verbatim with the CPU test emulation).
+ * The per-SB algorithm lives in me_core.h and the headers it includes (shared verbatim with the CPU test emulation).
  */
 #include <hip/hip_runtime.h>
 #include "me_core.h"
@@ -152,6 +152,33 @@ __global__ __launch_bounds__(256) void svt_sad_loop_kernel(const uint8_t *__rest
 /* the fields that may differ between the pictures of one launch (me_spec.h: everything else is constant inside a configuration) */
 static bool me_params_same_config(const svt_me_params *a, const svt_me_params *b) { return svt_hip_me_params_same_launch(a, b) != 0; }
 
+/* what every ME launch passes; a launch raises the kernel's dynamic LDS limit first when its layout needs more than the default 64 KB */
+struct me_launch_args {
+    hipStream_t stream; int blocks; const me_pic_dev *d; const svt_me_params *p; int n_sb, nx, W, H, total, chunk; unsigned long long *prof;
+};
+template <typename K, typename... X> static hipError_t me_launch_kernel(K kernel, const me_launch_args &a, const me_lds_layout &L, X... redo) {
+    if (L.total_bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L.total_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(a.blocks), dim3(256), L.total_bytes, a.stream, a.d, *a.p, L, a.n_sb, a.nx, a.W, a.H, a.total, a.chunk, a.prof, redo...);
+    return hipSuccess;
+}
+template <int S> static hipError_t me_dispatch_fast(const me_launch_args &a, const me_lds_layout &L) {
+    static_assert(me_spec_fast(S), "me_fast.h does not serve this specialisation");
+    return me_launch_kernel(svt_me_fast_kernel<S>, a, L);
+}
+/* d_redo: two launches where the compact layout (me_layout.h) buys a workgroup per CU: every SB with the compact layout Lc, then the SBs
+ * that flagged themselves (clipped search areas with tail columns: SBs near the right picture border) with the full one */
+template <int S> static hipError_t me_dispatch_sb(const me_launch_args &a, const me_lds_layout &L, const me_lds_layout &Lc, uint32_t *d_redo) {
+    if constexpr (me_spec_has_compact(S))
+        if (d_redo) {
+            const hipError_t e = me_launch_kernel(svt_me_sb_kernel<S, true>, a, Lc, d_redo);
+            return e != hipSuccess ? e : me_launch_kernel(svt_me_sb_kernel<S, false>, a, L, d_redo);
+        }
+    return me_launch_kernel(svt_me_sb_kernel<S, false>, a, L, (uint32_t *)nullptr);
+}
+
 /* params_stride = 0: one parameter set for every picture; 1: params[i] belongs to picture i */
 static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture *cur, const svt_pa_picture *ref0, const svt_pa_picture *ref1,
                          const svt_me_params *params_all, int params_stride, svt_me_pu_result *const *d_results, uint32_t *const *d_rcme) {
@@ -216,62 +243,33 @@ static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture 
 #ifdef ME_FINE_PROF
     { const char *sa = getenv("SVT_HIP_ME_STOP"); int v = sa ? atoi(sa) : -1; HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_me_stop_after), &v, sizeof v, 0, hipMemcpyHostToDevice, ctx->stream)); }
 #endif
-    /* compact layout: when the search area's width is a multiple of 8 and it buys a workgroup per CU (the 64 x 64-area presets) */
-    static const bool no_compact = getenv("SVT_HIP_ME_NOCOMPACT") != nullptr;
+    /* the instance specialised for the caller's parameter set when there is one (me_spec.h), else the generic one */
+    static const bool no_spec = getenv("SVT_HIP_ME_GENERIC") != nullptr;
+    static const bool no_fast = getenv("SVT_HIP_ME_NOFAST") != nullptr;
+    const int spec = no_spec ? 0 : me_spec_match(params);
+    /* compact layout: when the search area's width is a multiple of 8 and it buys a workgroup per CU (the 64 x 64-area presets), for the
+     * instances that are compiled with it */
     me_lds_layout Lc = L;
     uint32_t     *d_redo = nullptr;
-    if (!no_compact && (params->search_area_width & 7) == 0 && params->search_area_width <= 127 && me_lds_layout_compute_ex(params, &Lc, 1) == 0 &&
+    if (me_spec_has_compact(spec) && (params->search_area_width & 7) == 0 && params->search_area_width <= 127 && me_lds_layout_compute_ex(params, &Lc, 1) == 0 &&
         me_lds_workgroups_per_cu(&Lc) > me_lds_workgroups_per_cu(&L)) {
         d_redo = (uint32_t *)svt_ctx_slot(ctx, 39, (size_t)total * sizeof(uint32_t));
         if (!d_redo) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "me: redo flags");
         HIP_TRY(hipMemsetAsync(d_redo, 0, (size_t)total * sizeof(uint32_t), ctx->stream));
     }
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-    /* the instance specialised for the caller's parameter set when there is one (me_spec.h), else the generic one */
-    static const bool no_spec = getenv("SVT_HIP_ME_GENERIC") != nullptr;
-    static const bool no_fast = getenv("SVT_HIP_ME_NOFAST") != nullptr;
-    const int spec = no_spec ? 0 : me_spec_match(params);
-    ctx->me_instance = spec + (d_redo ? 200 : 0);
     /* me_fast.h's driver where a compiled instance of it serves the parameter set (me_spec_fast; today SPEC 1) */
-    bool fast_done = false;
-#define ME_LAUNCH_FAST(S) \
-    if constexpr (me_spec_fast(S)) { \
-        if (L.total_bytes > 64 * 1024) \
-            HIP_TRY(hipFuncSetAttribute((const void *)svt_me_fast_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, L.total_bytes)); \
-        ctx->me_instance = 100 + S; \
-        hipLaunchKernelGGL(svt_me_fast_kernel<S>, dim3(chunk * 8 * n_pics), dim3(256), L.total_bytes, ctx->stream, d, *params, L, n_sb, nx, W, H, total, chunk, d_prof); \
-        fast_done = true; \
-    }
-    if (fast_ok && !no_fast && !d_redo)
-        switch (spec) {
-        case 1: ME_LAUNCH_FAST(1); break;
-        default: break;
-        }
-#undef ME_LAUNCH_FAST
-    if (!fast_done)
+    const bool           fast = fast_ok && !no_fast && me_spec_fast(spec);
+    const me_launch_args a = {ctx->stream, chunk * 8 * n_pics, d, params, n_sb, nx, W, H, total, chunk, d_prof};
     switch (spec) {
-#define ME_LAUNCH(S) \
-    if (L.total_bytes > 64 * 1024) \
-        HIP_TRY(hipFuncSetAttribute((const void *)svt_me_sb_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, L.total_bytes)); \
-    hipLaunchKernelGGL(svt_me_sb_kernel<S>, dim3(chunk * 8 * n_pics), dim3(256), L.total_bytes, ctx->stream, d, *params, L, n_sb, nx, W, H, total, chunk, d_prof, (uint32_t *)nullptr)
-    /* two launches where the compact layout (me_layout.h) buys a workgroup per CU: every SB with the compact layout, then the SBs that
-     * flagged themselves (clipped search areas with tail columns: SBs near the right picture border) with the full one */
-#define ME_LAUNCH2(S) \
-    if (d_redo) { \
-        if (Lc.total_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)svt_me_sb_kernel<S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Lc.total_bytes)); \
-        if (L.total_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)svt_me_sb_kernel<S, false>, hipFuncAttributeMaxDynamicSharedMemorySize, L.total_bytes)); \
-        hipLaunchKernelGGL((svt_me_sb_kernel<S, true>), dim3(chunk * 8 * n_pics), dim3(256), Lc.total_bytes, ctx->stream, d, *params, Lc, n_sb, nx, W, H, total, chunk, d_prof, d_redo); \
-        hipLaunchKernelGGL((svt_me_sb_kernel<S, false>), dim3(chunk * 8 * n_pics), dim3(256), L.total_bytes, ctx->stream, d, *params, L, n_sb, nx, W, H, total, chunk, d_prof, d_redo); \
-    } else { ME_LAUNCH(S); }
-    case 1: ME_LAUNCH(1); break;
-    case 2: ME_LAUNCH(2); break;
-    case 3: ME_LAUNCH(3); break;
-    case 4: ME_LAUNCH2(4); break;
-    case 5: ME_LAUNCH2(5); break;
-    default: ME_LAUNCH2(0); break;
-#undef ME_LAUNCH2
-#undef ME_LAUNCH
+    case 1: HIP_TRY(fast ? me_dispatch_fast<1>(a, L) : me_dispatch_sb<1>(a, L, Lc, d_redo)); break;
+    case 2: HIP_TRY(me_dispatch_sb<2>(a, L, Lc, d_redo)); break;
+    case 3: HIP_TRY(me_dispatch_sb<3>(a, L, Lc, d_redo)); break;
+    case 4: HIP_TRY(me_dispatch_sb<4>(a, L, Lc, d_redo)); break;
+    case 5: HIP_TRY(me_dispatch_sb<5>(a, L, Lc, d_redo)); break;
+    default: HIP_TRY(me_dispatch_sb<0>(a, L, Lc, d_redo)); break;
     }
+    ctx->me_instance = spec + (fast ? 100 : d_redo ? 200 : 0); /* (d_redo: me_dispatch_sb issued the compact layout's two launches) */
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
     if (d_prof) {

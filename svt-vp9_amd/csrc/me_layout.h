@@ -1,7 +1,7 @@
 /* me_layout.h -- host-side computation of the ME kernel's LDS layout from the search parameters. */
 #ifndef SVT_ME_LAYOUT_H
 #define SVT_ME_LAYOUT_H
-#include "me_core.h"
+#include "me_types.h"
 
 #if defined(__HIPCC__)
 #define ME_LAYOUT_FN __host__ __device__ static inline
@@ -51,7 +51,7 @@ ME_LAYOUT_FN void me_lds_layout_geom_ex(const svt_me_params *p, me_lds_layout *L
     L->off_cand_hi   = -1;
     if (L->cand_dwords > 168) { L->off_cand_hi = off; off += (L->cand_dwords - 168) * 2; }
     L->off_pred0     = off;
-#ifdef SVT_HOST_EMU /* the kernel keeps list 0's prediction dwords in registers */
+#ifdef SVT_HOST_EMU /* data, not a path: the bytes behind ME_PR (me_prims_emu.h); the kernel keeps list 0's prediction dwords in registers */
     if (p->num_ref_lists == 2) off += 16 * 256 * 4;
 #endif
     L->total_bytes = off;

@@ -37,6 +37,10 @@ constexpr bool me_spec_fast(int spec) {
            ME_SPECS[spec - 1].cu16 == 0 && ME_SPECS[spec - 1].cu8 == 1;
 }
 
+/* the instances that are also compiled for the compact LDS layout (me_layout.h; svt_me_sb_kernel<SPEC, true>): the generic one and the
+ * 64 x 64-area presets, where it buys a second workgroup per CU -- for SPEC 1-3 it buys none (31 744 -> 30 512 bytes: five either way) */
+constexpr bool me_spec_has_compact(int spec) { return spec == 0 || spec == 4 || spec == 5; }
+
 /* overwrite the configuration-constant fields of *p with the constants of SPEC (1..ME_SPEC_COUNT) */
 template <int SPEC> __host__ __device__ inline void me_spec_apply(svt_me_params *p) {
     static_assert(SPEC >= 1 && SPEC <= ME_SPEC_COUNT, "no such specialisation");

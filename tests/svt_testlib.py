@@ -1,6 +1,7 @@
 """Shared helpers for tests/, bench.py and __graft_entry__.smoke(): synthetic clips, PA planes,
 loading the product binding and the parity oracle (oracle/ is test infrastructure; see oracle/oracle_me.c)."""
 import ctypes as C
+import glob
 import importlib.util
 import os
 import struct
@@ -255,8 +256,7 @@ def emu():
     if _emu is None:
         d = os.path.join(ROOT, "tests", "emu")
         so = os.path.join(d, "libme_emu.so")
-        srcs = [os.path.join(d, "me_emu.c"), os.path.join(ROOT, "svt-vp9_amd", "csrc", "me_core.h"),
-                os.path.join(ROOT, "svt-vp9_amd", "csrc", "me_layout.h")]
+        srcs = [os.path.join(d, "me_emu.c")] + glob.glob(os.path.join(ROOT, "svt-vp9_amd", "csrc", "me_*.h"))
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.check_call(["gcc", "-std=gnu11", "-O2", "-fPIC", "-shared", "-Wno-unused-function", "-o", so,
                                    srcs[0]])

@@ -96,7 +96,7 @@ def test_me_wide_search_area_and_empty_area(ctx):
 @pytest.mark.parametrize("wh", [(64, 32), (48, 48), (32, 64), (64, 64), (40, 56), (16, 127)])
 def test_me_large_search_areas_full_pel_layouts(ctx, wh):
     """The fused full-pel phase has two lane layouts: areas of at least 2048 positions whose width is a multiple of 16 take the run-walking
-    16x16-PU layout (csrc/me_core.h me_fullpel_fused16_dev), the others the 8x8-block one (width 40: two groups per iteration; 16 x 127: a
+    16x16-PU layout (csrc/me_fullpel.h me_fullpel_fused16_dev), the others the 8x8-block one (width 40: two groups per iteration; 16 x 127: a
     tall, narrow area, runs numbered down the columns).  All of them against the oracle, on a clip with sub-pel motion and on flat pictures
     (every position ties: the first minimum in raster order has to come out of the key minima whatever the order the lanes visit positions in)."""
     pics = [T.PaPic(f) for f in T.gen_clip_subpel(264, 200, 3, 29)]
