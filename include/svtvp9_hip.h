@@ -175,10 +175,11 @@ int32_t svt_hip_me_last_instance(const svt_hip_ctx *ctx);
  * widths that are multiples of 8; the launcher takes it where it buys a workgroup per CU: 160 KB per CU in granules of 1 280 bytes).  Negative: no such layout. */
 int32_t svt_hip_me_lds_bytes(const svt_me_params *p, int32_t compact);
 /* Deployment knob of the intra encode pass (svt_hip_encdec_intra_device, and the intra blocks of inter pictures) launched on ctx: at most n
- * one-wave workgroups (0 = the default: two per compute unit, the lowest latency for a key frame alone).  A pass that runs
- * BESIDE other work of the device (a key frame of the next GOP beside the current one) leaves more of it to that work with fewer: every CU
- * that hosts one of its waves has registers for one motion-estimation workgroup less (128: 7.9 ms alone, +2 % for the pipelined step of
- * bench.py).  The environment's SVT_HIP_INTRA_WGS sets the process-wide default. */
+ * 64-lane WORKERS (0 = the default: two per compute unit, the lowest latency for a key frame alone).  A worker is one wave; the launch packs four
+ * of them into each 256-thread workgroup (n = 128: 32 workgroups), so the name of the call is historical -- until the packing a worker was a
+ * workgroup.  A pass that runs BESIDE other work of the device (a key frame of the next GOP beside the current one) leaves more of it to that work
+ * with fewer: every CU that hosts one of its WORKGROUPS -- up to four workers, one per SIMD -- has registers and LDS for one motion-estimation
+ * workgroup less (128: 7.9 ms alone).  The environment's SVT_HIP_INTRA_WGS sets the process-wide default, in workers as well. */
 int32_t svt_hip_ctx_set_intra_workgroups(svt_hip_ctx *ctx, int32_t n);
 /* submits an empty kernel to the context's stream and waits: the stream's hardware queue exists afterwards (the runtime creates it at the first
  * submission, 1-3 ms on the submitting thread).  For hosts that time a stream from its first picture (the encoder library's init does this). */

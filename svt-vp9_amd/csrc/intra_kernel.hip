@@ -20,14 +20,15 @@
  * above-right neighbour the reference's z-order is only ONE of the orders that give its result.  The picture is cut into 32x32 luma
  * areas (the largest block here); the blocks of an area are coded one after the other (z-order) and area (r, c) can start when
  * (r, c - 1) and (r - 1, c) are done: an anti-diagonal wavefront over the areas, times three independent planes.  One 64-lane
- * workgroup codes one (area, plane) at a time; the workgroups (one per CU, persistent) take TICKETS (an atomic counter) that enumerate
- * the (area, plane) pairs diagonal by diagonal, so a workgroup only ever waits for tickets smaller than its own -- which are held by
- * workgroups that already run or are done: no deadlock whatever the dispatch order, no co-residency requirement.  A block is N x N
+ * WORKER (a wave) codes one (area, plane) at a time; the workers (persistent) take TICKETS (an atomic counter) that enumerate
+ * the (area, plane) pairs diagonal by diagonal, so a worker only ever waits for tickets smaller than its own -- which are held by
+ * workers that already run or are done: no deadlock whatever the dispatch order, no co-residency requirement.  Four workers are
+ * packed into one 256-thread workgroup (see svt_intra_kernel): they share nothing but the launch.  A block is N x N
  * with N lanes active (lane i = row i of the prediction, then column / row i of the transform); the chain of dependent blocks, not
  * the lane count, bounds the speed: a 2160p key frame is 187 diagonals of at most 68 areas.  This kernel is latency-bound by design (one picture in a GOP); it shares the GPU with
  * the batches of the inter pictures running beside it.
- * Visibility between workgroups (other CUs, other XCDs' L2): release fence + flag store when an area is done, flag load + acquire
- * fence before the first reference-sample load; inside a workgroup the block's stores are drained (workgroup fence) before the
+ * Visibility between workers (other CUs, other XCDs' L2): release fence + flag store when an area is done, flag load + acquire
+ * fence before the first reference-sample load; inside a worker the block's stores are drained (workgroup fence) before the
  * next block reads them.
  */
 #include <hip/hip_runtime.h>
@@ -56,11 +57,11 @@ struct intra_pic_dev {
     int32_t        mixed;   /* 1: an inter picture with some intra blocks: inter blocks are skipped (the batch coded them) */
 };
 
-/* Visibility of a block's reconstruction to the workgroups that predict from it (other CUs, other XCDs): written through and read
+/* Visibility of a block's reconstruction to the workers that predict from it (other CUs, other XCDs): written through and read
  * with agent-scope accesses (the deblocking kernel's seam-row scheme), NOT with a release / acquire fence pair per area: such a pair
  * is buffer_wbl2 sc1 + buffer_inv sc1 -- write-back and invalidation of the XCD's whole L2 -- 18 000 times per 2160p key frame, paid by
  * every kernel that runs beside this one (measured in the step: a key frame cost + 4 ms of step time with the fences, however few
- * workgroups coded it).  -DINTRA_FENCES restores the fence form (3-12 % faster when the pass has the GPU to itself). */
+ * workers coded it).  -DINTRA_FENCES restores the fence form (3-12 % faster when the pass has the GPU to itself). */
 #ifdef INTRA_FENCES
 #define INTRA_WT false
 #define INTRA_LD(p) (*(p))
@@ -74,10 +75,19 @@ __device__ unsigned long long g_intra_fine[8];
 #else
 #define IPF(k) ((void)0)
 #endif
-/* one N x N transform block of plane `plane` at sample (x0, y0) of that plane; the whole workgroup (one wave) calls it */
+/* a worker's slice of the workgroup's LDS: the transform tiles (two 32 x 33 dword tiles: the idle half of the wave runs along on its
+ * own), then the 128 reference samples */
+#define INTRA_TILE_DW  (2 * 32 * 33)
+#define INTRA_SLICE_DW (INTRA_TILE_DW + 128 / 4)
+#define INTRA_W        4 /* workers per workgroup */
+/* one N x N transform block of plane `plane` at sample (x0, y0) of that plane; the whole worker (one wave) calls it.  lds: the
+ * workgroup's LDS.  The worker's slice is derived HERE, per block: carried in registers from the kernel's top across every block size's
+ * body it cost well over 100 B of scratch per lane (816 B; this way the kernel holds 676 B, its one-worker predecessor held 684). */
 template <int N>
-__device__ __forceinline__ int intra_block(const intra_pic_dev &P, int plane, int x0, int y0, int mode, int sb, int32_t *tile, uint8_t *edge, int have_right = 0) {
-    const int lane = (int)threadIdx.x, c = plane ? 1 : 0;
+__device__ __forceinline__ int intra_block(const intra_pic_dev &P, int plane, int x0, int y0, int mode, int sb, int32_t *lds, int have_right = 0) {
+    const int lane = (int)__lane_id(), c = plane ? 1 : 0;
+    int32_t *const tile = lds + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) * INTRA_SLICE_DW;
+    uint8_t *const edge = (uint8_t *)(tile + INTRA_TILE_DW);
     const int rs = P.rec_stride[c];
     uint8_t  *rp = P.rec[plane];
     const int have_left = x0 > 0, have_top = y0 > 0;
@@ -110,7 +120,7 @@ __device__ __forceinline__ int intra_block(const intra_pic_dev &P, int plane, in
         }
         if (lane == 0) edge[32] = have_top ? (have_left ? INTRA_LD(&rp[(size_t)(y0 - 1) * rs + x0 - 1]) : (uint8_t)129) : (uint8_t)127;
     }
-    __syncthreads();
+    tq_block_sync(); /* edge[] is written and read by this wave alone */
     IPF(0); /* source issue + reference samples into LDS */
     intra_pred_row<N>(edge, mode, i, have_left, have_top, prow);
     {
@@ -137,7 +147,7 @@ __device__ __forceinline__ int intra_block(const intra_pic_dev &P, int plane, in
     IPF(2); /* transform / quantisation / reconstruction */
     /* the block's reconstruction is read by the next block of this wave: drain the stores */
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __syncthreads();
+    tq_block_sync();
     IPF(3); /* store drain */
     return __builtin_amdgcn_readfirstlane(eob);
 }
@@ -147,44 +157,64 @@ __device__ __forceinline__ int intra_block(const intra_pic_dev &P, int plane, in
 #endif
 /* Register budget: left alone the compiler takes 308 VGPRs for this kernel -- one such wave per CU, resident for milliseconds, leaves
  * its SIMD room for two motion-estimation waves instead of five, i.e. the CU two ME workgroups instead of five (measured in the step:
- * + 4 ms per key frame, whatever the number of workgroups of this launch).  Held to 128 it spills the 32x32 path's transform rows
- * to scratch, but displaces one ME wave, not three. */
+ * + 4 ms per key frame, whatever the number of workers of this launch).  Held to 128 it spills the 32x32 path's transform rows
+ * to scratch, but displaces one ME wave, not three.
+ *
+ * Packing: a workgroup is W independent 64-lane WORKERS (waves), each with its own slice of the LDS.  Beside the 2160p ME instance
+ * (five four-wave workgroups fill a CU: 96 VGPRs x 5 waves per SIMD, 25 of 128 LDS granules each) a 128-VGPR wave takes the registers
+ * of one ME wave on its SIMD, i.e. one whole ME workgroup off its CU -- as a one-wave workgroup just as much as four waves, one per
+ * SIMD, do.  W = 4 puts four workers into that one hole: 4 x (8 448 + 128) B = 34 304 B = 27 LDS granules of 1 280 B, which with four ME
+ * workgroups is 127 of 128.
+ * The workers of a workgroup NEVER meet: they draw different tickets, loop different numbers of times and leave at different
+ * moments, so there is no workgroup barrier anywhere in this kernel (one s_barrier would hang it) -- every rendezvous is of the lanes
+ * of ONE wave (tq_block_sync: LDS and memory accesses of a wave are issued in order; what has to be kept is the compiler's order).
+ * Deadlock: a worker waits only at the flags of cells with SMALLER tickets than its own.  A ticket exists only because a worker that
+ * was already running drew it, and a running wave keeps running whatever its workgroup-mates do (no barrier, no shared state): so
+ * the holder of the smallest unfinished ticket waits for nothing and finishes, then the next -- whatever the dispatch order, however
+ * few workers are resident, and whichever of them share a workgroup. */
 #ifdef INTRA_NUM_VGPR
 __attribute__((amdgpu_num_vgpr(INTRA_NUM_VGPR)))
 #endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INTRA_WAVES_PER_EU, INTRA_WAVES_PER_EU))) void svt_intra_kernel(const intra_pic_dev P) {
-    __shared__ int32_t tile[2 * 32 * 33];
-    __shared__ uint8_t edge[128];
-    __shared__ int32_t s_ticket;
+__global__ __launch_bounds__(64 * INTRA_W) __attribute__((amdgpu_waves_per_eu(INTRA_WAVES_PER_EU, INTRA_WAVES_PER_EU))) void svt_intra_kernel(const intra_pic_dev P, const int n_workers) {
+    constexpr int W = INTRA_W;
+    __shared__ int32_t s_lds[W * INTRA_SLICE_DW];
+    /* the worker: wave-uniform, and known to be so (readfirstlane) -- it selects the LDS slice with scalar arithmetic */
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if ((int)blockIdx.x * W + wave >= n_workers) return; /* the last workgroup of a launch whose worker count is no multiple of W */
     /* The unit of scheduling is a 16x16 luma CELL (8x8 in the chroma planes) -- round 6; until then a 32x32 area, whose four 16x16 blocks ran
      * one after the other behind ONE pair of flags: a 2160p key frame was 187 diagonals of 4 block steps.  Intra prediction of blocks >= 8x8
      * never reads the above-right neighbour, so any order in which a block follows its left, above and above-left neighbours gives the
      * reference's result: cells go in anti-diagonal order (374 diagonals of ONE 16x16 step at 2160p), the blocks inside a cell in z-order.
      * A cell's flag says "this cell and everything it depended on is reconstructed and visible".  A 32x32 block covers 2 x 2 cells: it is
-     * coded by the ticket of its TOP-RIGHT cell -- every cell it depends on then lies on an earlier diagonal, so a workgroup still only ever
+     * coded by the ticket of its TOP-RIGHT cell -- every cell it depends on then lies on an earlier diagonal, so a worker still only ever
      * waits for smaller tickets -- which sets all four flags; the tickets of its other three cells have nothing to do. */
-    const int lane = (int)threadIdx.x, c_cols = (P.width + 15) >> 4, c_rows = (P.height + 15) >> 4, n_cell = c_cols * c_rows;
+    const int lane = (int)__lane_id(), c_cols = (P.width + 15) >> 4, c_rows = (P.height + 15) >> 4, n_cell = c_cols * c_rows;
     const int n_diag = c_rows + c_cols - 1;
-    /* one wave per CU on a chain of dependent blocks, beside kernels that fill the SIMDs: it issues rarely, so letting it go first costs
+    /* a wave on a chain of dependent blocks, beside kernels that fill the SIMDs: it issues rarely, so letting it go first costs
      * the others next to nothing and keeps the chain at the speed it has alone */
     __builtin_amdgcn_s_setprio(3);
-  /* workgroups are persistent: each keeps drawing tickets until they run out -- a launch of one workgroup per (cell, plane) would keep
+  /* workers are persistent: each keeps drawing tickets until they run out -- a launch of one worker per (cell, plane) would keep
      thousands of them resident, nearly all polling flags of cells many diagonals away */
 #ifdef INTRA_PROF
   unsigned long long pf[5] = {0, 0, 0, 0, 0}, pf_n = 0;
+  const int worker = (int)blockIdx.x * W + wave;
 #endif
   for (;;) {
-    __syncthreads(); /* (s_ticket of the previous round has been read by every lane) */
-    if (lane == 0) s_ticket = atomicAdd(&P.sync[0], 1);
-    __syncthreads();
+    /* lane 0 draws; the ticket reaches the wave's other lanes through a scalar register.  The wave meets first: without a convergent
+     * operation between the `if (lane == 0)` that closes a round and the one that draws, the compiler threads the two into a path of
+     * lane 0's own around the loop, and the lanes no longer arrive at the readfirstlane together */
+    tq_block_sync();
+    int drawn = 0;
+    if (lane == 0) drawn = atomicAdd(&P.sync[0], 1);
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
 #ifdef INTRA_PROF
-    if (s_ticket >= 3 * n_cell) { if (lane == 0 && blockIdx.x == 0) printf("[intra-fine] refs %llu predict %llu tq %llu drain %llu (summed over all workgroups so far)\n", g_intra_fine[0], g_intra_fine[1], g_intra_fine[2], g_intra_fine[3]);
-      if (lane == 0 && blockIdx.x < 2) printf("[intra-prof] wg %d cells %llu: ticket+map %llu wait %llu work %llu drain %llu publish %llu (100 MHz ticks)\n", (int)blockIdx.x, pf_n, pf[0], pf[1], pf[2], pf[3], pf[4]); break; }
+    if (ticket >= 3 * n_cell) { if (lane == 0 && worker == 0) printf("[intra-fine] refs %llu predict %llu tq %llu drain %llu (summed over all workers so far)\n", g_intra_fine[0], g_intra_fine[1], g_intra_fine[2], g_intra_fine[3]);
+      if (lane == 0 && worker < 2) printf("[intra-prof] worker %d cells %llu: ticket+map %llu wait %llu work %llu drain %llu publish %llu (100 MHz ticks)\n", worker, pf_n, pf[0], pf[1], pf[2], pf[3], pf[4]); break; }
     unsigned long long pt0 = __builtin_amdgcn_s_memtime();
 #else
-    if (s_ticket >= 3 * n_cell) break;
+    if (ticket >= 3 * n_cell) break;
 #endif
-    const int ticket = s_ticket, plane = ticket % 3;
+    const int plane = ticket % 3;
     /* the n-th cell in anti-diagonal order (diagonal d = row + col, rows ascending inside a diagonal): cells before diagonal d in closed form
      * (growing part d (d + 1) / 2, then full diagonals of m = min(rows, cols) cells, then the shrinking tail), d by bisection */
     const int n = ticket / 3, m = c_rows < c_cols ? c_rows : c_cols, M = c_rows < c_cols ? c_cols : c_rows;
@@ -220,7 +250,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INTRA_WAVES_
         if (wl_c >= 0) while (__hip_atomic_load(&done[wl_r * c_cols + wl_c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(2);
         if (wa_r >= 0) while (__hip_atomic_load(&done[wa_r * c_cols + wa_c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(2);
     }
-    __syncthreads();
+    tq_block_sync(); /* the wave's reference-sample loads stay behind lane 0's flag loads */
 #ifdef INTRA_FENCES
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
@@ -254,13 +284,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INTRA_WAVES_
             for (int q4 = 0; q4 < 4; q4++) {
                 const int mq = (m4 >> (4 * q4)) & 15;
                 if (mq > 9) { if (lane == 0) atomicOr(P.status, 1); continue; }
-                eob |= intra_block<4>(P, 0, x0 + 4 * (q4 & 1), y0 + 4 * (q4 >> 1), mq, sb, tile, edge, !(q4 & 1));
+                eob |= intra_block<4>(P, 0, x0 + 4 * (q4 & 1), y0 + 4 * (q4 >> 1), mq, sb, s_lds, !(q4 & 1));
             }
         }
-        else if (nn == 32) eob = intra_block<32>(P, plane, x0, y0, mode, sb, tile, edge);
-        else if (nn == 16) eob = intra_block<16>(P, plane, x0, y0, mode, sb, tile, edge);
-        else if (nn == 8) eob = intra_block<8>(P, plane, x0, y0, mode, sb, tile, edge);
-        else eob = intra_block<4>(P, plane, x0, y0, mode, sb, tile, edge);
+        else if (nn == 32) eob = intra_block<32>(P, plane, x0, y0, mode, sb, s_lds);
+        else if (nn == 16) eob = intra_block<16>(P, plane, x0, y0, mode, sb, s_lds);
+        else if (nn == 8) eob = intra_block<8>(P, plane, x0, y0, mode, sb, s_lds);
+        else eob = intra_block<4>(P, plane, x0, y0, mode, sb, s_lds);
         if (eob && lane == 0) P.nz[ur * P.mi_stride + uc] = 1; /* the three planes of a block may all store the same 1 */
     }
 #ifdef INTRA_PROF
@@ -269,10 +299,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INTRA_WAVES_
     /* publish the cell (the four cells of a 32x32 block): its reconstruction reaches memory before the flag does */
 #ifdef INTRA_FENCES
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
+    tq_block_sync();
 #else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* every (write-through) store of this wave has completed */
-    __syncthreads();
+    tq_block_sync(); /* ... and lane 0's flag store stays behind it */
 #endif
 #ifdef INTRA_PROF
     unsigned long long pt4 = __builtin_amdgcn_s_memtime();
@@ -325,13 +355,14 @@ int32_t svt_intra_launch(svt_hip_ctx *ctx, const svt_encdec_picture *p, int32_t 
     const int n_cell = ((width + 15) >> 4) * ((height + 15) >> 4); /* 16x16 luma cells: the unit of the wavefront */
     HIP_TRY(hipMemsetAsync(d_sync, 0, (size_t)(2 + 3 * n_cell) * sizeof(int32_t), ctx->stream));
     /* (function-local statics with an initialiser: initialised once, thread-safely -- several contexts may launch from several threads) */
-    static const int wg_per_cu = [] { const char *e = getenv("SVT_HIP_INTRA_WG_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 2; }(); /* two: a diagonal's tickets are then mostly held by workgroups already waiting at their flags (2160p, 16x16 DC: 4.77 -> 4.34 ms) */
-    static const int wg_cap = [] { const char *e = getenv("SVT_HIP_INTRA_WGS"); return e && atoi(e) > 0 ? atoi(e) : 0; }(); /* deployment knob: fewer workgroups = a longer pass that leaves more of the device to what runs beside it (bench.py: 128) */
-    int grid = ctx->cu_count * wg_per_cu;
-    const int cap = ctx->intra_wgs > 0 ? ctx->intra_wgs : wg_cap; /* the context's setting (svt_hip_ctx_set_intra_workgroups) before the environment's */
-    if (cap && grid > cap) grid = cap;
-    if (grid > 3 * n_cell) grid = 3 * n_cell;
-    hipLaunchKernelGGL(svt_intra_kernel, dim3(grid), dim3(64), 0, ctx->stream, P);
+    /* numbers of 64-lane WORKERS (the names of the knobs date from one worker per workgroup) */
+    static const int wk_per_cu = [] { const char *e = getenv("SVT_HIP_INTRA_WG_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 2; }(); /* two: a diagonal's tickets are then mostly held by workers already waiting at their flags (2160p, 16x16 DC: 4.77 -> 4.34 ms) */
+    static const int wk_cap = [] { const char *e = getenv("SVT_HIP_INTRA_WGS"); return e && atoi(e) > 0 ? atoi(e) : 0; }(); /* deployment knob: fewer workers = a longer pass that leaves more of the device to what runs beside it (bench.py: 128) */
+    int workers = ctx->cu_count * wk_per_cu;
+    const int cap = ctx->intra_wgs > 0 ? ctx->intra_wgs : wk_cap; /* the context's setting (svt_hip_ctx_set_intra_workgroups) before the environment's */
+    if (cap && workers > cap) workers = cap;
+    if (workers > 3 * n_cell) workers = 3 * n_cell;
+    hipLaunchKernelGGL(svt_intra_kernel, dim3((workers + INTRA_W - 1) / INTRA_W), dim3(64 * INTRA_W), 0, ctx->stream, P, workers);
     HIP_TRY(hipGetLastError());
     return SVT_HIP_OK;
 }
