@@ -734,6 +734,82 @@ int32_t svt_hip_coeff_rate_batch(svt_hip_ctx *ctx, const int16_t *qcoeff, size_t
                                  int32_t *bits);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Coefficient tokenisation: the data-parallel half of entropy coding.
+ *
+ * Replaces eb_vp9_tokenize_sb -> tokenize_b (VPX/vp9_tokenize.c:275-349, 397-430) as eb_vp9_entropy_coding_kernel calls it for
+ * every coded block in front of the bool coder (Codec/EbEntropyCodingProcess.c:381-398).  The reference codes with the default
+ * probabilities (its count-based update is compiled out, VPX/vp9_tokenize.c:301-304), so a token stream plus the fixed tables is
+ * all the arithmetic coder needs; the coder itself, the headers and the packets stay on the host.
+ *
+ * One token = one uint32_t record: extra << 16 | prob_row << 4 | token.
+ *   token     ZERO 0, ONE..FOUR 1..4, CAT1..CAT6 5..10 (|v| 5-6, 7-10, 11-18, 19-34, 35-66, >= 67), EOB 11 (at scan position eob
+ *             when eob < n) -- VPX/vp9_entropy.h:28-52
+ *   extra     ((|v| - base of the token) << 1 | (v < 0)) & 0xffff: the reference's int16 EXTRABIT (VPX/vp9_tokenize.h:34, 100-111); 0
+ *             for ZERO and EOB
+ *   prob_row  (((tx_size * 2 + plane_type) * 2 + is_inter) * 6 + band) * 6 + ctx (< 576): TOKENEXTRA.context_tree =
+ *             &coef_probs[0][0][0][0][0][0] + 3 * prob_row
+ * counts[SVT_TOK_COUNTS] = td->rd_counts.coef_counts[tx_size][plane_type][is_inter][band][ctx][token] = counts[prob_row * 12 + token]
+ * (eob_branch is compiled out in the reference and is not produced). */
+#define SVT_TOK_EOB 11
+#define SVT_TOK_COUNTS 6912   /* 4 * 2 * 2 * 6 * 6 * 12 */
+#define SVT_TOK_NONE 0xFFFFFFFFu
+#define SVT_TOK_TOKEN(rec) ((uint32_t)(rec) & 15u)
+#define SVT_TOK_PROB_ROW(rec) (((uint32_t)(rec) >> 4) & 0xfffu)
+#define SVT_TOK_EXTRA(rec) ((uint32_t)(rec) >> 16)
+#define SVT_TOK_RECORD(extra, prob_row, token) ((uint32_t)(extra) << 16 | (uint32_t)(prob_row) << 4 | (uint32_t)(token))
+
+/* host: the scan orders the tokeniser (and the rate estimation) walk, in the canonical layout svt_rate_block.scan_off addresses:
+ * for tx_size 0..3, for tx_type 0..3 {scan[n], neighbors[2 (n + 1)]} = eb_vp9_scan_orders[tx_size][tx_type].scan / .neighbors
+ * (VPX/vp9_scan.c); offsets16[tx_size * 4 + tx_type] = element offset of a table.  Built at first use from the committed inverse
+ * scans (svt_hip_vp9_iscan_tables) and the neighbour rule of csrc/tokenize_core.h. */
+const int16_t *svt_hip_vp9_scan_tables(const uint32_t **offsets16, int32_t *entries);
+
+/* Block-level form = tokenize_b per block (VPX/vp9_tokenize.c:275-349): the blocks are the records the rate estimation takes, their
+ * scan_off in the canonical layout (it names the transform type).  d_tok_off[n_blocks + 1] is WRITTEN: block b's tokens are
+ * d_tokens[d_tok_off[b] .. d_tok_off[b + 1]), eob + (eob < n) of them, in scan order; the last entry is the total.  Nothing is
+ * written at or beyond d_tokens + capacity (a total above capacity tells the caller; the contents are then unspecified).  d_counts
+ * (SVT_TOK_COUNTS, may be NULL) is overwritten.  Asynchronous on the context's stream. */
+int32_t svt_hip_tokenize_blocks_device(svt_hip_ctx *ctx, const int16_t *d_qcoeff, const svt_rate_block *d_blocks, int32_t n_blocks,
+                                       uint32_t *d_tokens, uint32_t capacity, uint32_t *d_tok_off, uint32_t *d_counts);
+/* Host-pointer convenience form. */
+int32_t svt_hip_tokenize_blocks(svt_hip_ctx *ctx, const int16_t *qcoeff, size_t coeff_count, const svt_rate_block *blocks, int32_t n_blocks,
+                                uint32_t *tokens, uint32_t capacity, uint32_t *tok_off, uint32_t *counts);
+
+/* host form of the block-level tokeniser (the same text, csrc/tokenize_core.h), pure CPU, host pointers; validates the blocks */
+int32_t svt_hip_tokenize_blocks_host(const int16_t *qcoeff, size_t coeff_count, const svt_rate_block *blocks, int32_t n_blocks, uint32_t *tokens,
+                                     uint32_t capacity, uint32_t *tok_off, uint32_t *counts);
+
+/* Picture-level form = eb_vp9_tokenize_sb over every coded block of a picture (VPX/vp9_tokenize.c:397-430 as
+ * Codec/EbEntropyCodingProcess.c:381-398 calls it, above / left entropy contexts cleared as :88-105 clears them for the one tile),
+ * from what svt_hip_encdec_batch_device / svt_hip_encdec_intra_device leave on the device: the grid with its skip flags, the
+ * position-addressed coefficients, the eob map.  A skipped block emits nothing and its contexts are 0; every transform block of a
+ * coded block emits eob + (eob < n) tokens.  Token order = coefficient order: SBs raster; inside an SB Y, Cb, Cr; inside a plane area
+ * transform blocks in z-order of their origin unit; inside a block scan order.
+ *   d_tok_off  shape of the eob map: at the origin unit of every transform block of a coded block the offset of its first token,
+ *              SVT_TOK_NONE everywhere else
+ *   d_sb_off   n_sb + 1 entries: first token of every SB; the last entry is the picture's total, written ALWAYS.  When it exceeds
+ *              capacity nothing is written at or beyond d_tokens + capacity and the contents are unspecified
+ *   d_counts   SVT_TOK_COUNTS entries, overwritten; may be NULL */
+typedef struct svt_tok_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const int16_t          *d_qcoeff;   /* n_sb * SVT_SB_COEFFS, 16-byte aligned */
+    const uint16_t         *d_eob_map;
+    uint32_t               *d_tokens;
+    uint32_t                capacity;   /* records d_tokens can hold */
+    uint32_t                pad_;
+    uint32_t               *d_tok_off;
+    uint32_t               *d_sb_off;
+    uint32_t               *d_counts;
+} svt_tok_picture;
+/* n_pics (<= 32) pictures of one geometry in one call (host array of descriptors holding device pointers).  Asynchronous on the
+ * context's stream: behind svt_hip_encdec_batch_device / svt_hip_encdec_intra_device on the same context it needs no host round trip. */
+int32_t svt_hip_tokenize_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_tok_picture *pics, int32_t width, int32_t height, int32_t mi_stride);
+/* host form of the same text (csrc/tokenize_core.h), pure CPU; the svt_tok_picture fields are host pointers */
+int32_t svt_hip_tokenize_picture(const svt_tok_picture *pic, int32_t width, int32_t height, int32_t mi_stride);
+/* records a picture emits at most: every coefficient a token (W*H*3/2), plus room for an EOB token per 4x4 block (W*H*3/32) */
+uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.
  *
  * Replaces, per batch of mutually independent pictures (e.g. the pictures of one temporal layer of a mini-GOP), the data path of

@@ -146,6 +146,15 @@ class EncdecPicture(C.Structure):
 
 SB_COEFFS = 6144
 
+
+class TokPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_qcoeff", C.c_void_p), ("d_eob_map", C.c_void_p), ("d_tokens", C.c_void_p), ("capacity", C.c_uint32),
+                ("pad_", C.c_uint32), ("d_tok_off", C.c_void_p), ("d_sb_off", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+TOK_COUNTS = 6912
+TOK_NONE = 0xFFFFFFFF
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -174,6 +183,8 @@ EXPORTS = [
     "svt_hip_me_last_instance", "svt_hip_me_lds_bytes", "svt_hip_vp9_layer_qindex", "svt_hip_mem_upload_2d_direct", "svt_hip_mem_upload_wait", "svt_hip_host_unregister_all", "svt_hip_host_registry_retain", "svt_hip_host_registry_release",
     "svt_hip_intra_search_device", "svt_hip_md_intra_search_device", "svt_hip_md_intra_search_picture",
     "svt_hip_pa_noise_params_derive", "svt_hip_pa_noise_batch_device", "svt_hip_pa_histogram_batch_device", "svt_hip_pa_chroma_mean_batch_device",
+    "svt_hip_vp9_scan_tables", "svt_hip_tokenize_blocks_device", "svt_hip_tokenize_blocks", "svt_hip_tokenize_blocks_host", "svt_hip_tokenize_batch_device", "svt_hip_tokenize_picture",
+    "svt_hip_tokenize_capacity",
 ]
 
 _lib = None
@@ -201,6 +212,9 @@ def load():
         _lib.svt_hip_lf_thresh_init.restype = None
         _lib.svt_hip_vp9_iscan_tables.restype = C.POINTER(C.c_int16)
         _lib.svt_hip_vp9_iscan_tables.argtypes = [C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_int32)]
+        _lib.svt_hip_vp9_scan_tables.restype = C.POINTER(C.c_int16)
+        _lib.svt_hip_vp9_scan_tables.argtypes = [C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_int32)]
+        _lib.svt_hip_tokenize_capacity.restype = C.c_uint32
         _lib.svt_hip_encdec_work_destroy.restype = None
         _lib.svt_hip_host_free.restype = None
         _lib.svt_hip_encdec_work_set_stage_hook.restype = None
