@@ -810,6 +810,69 @@ int32_t svt_hip_tokenize_picture(const svt_tok_picture *pic, int32_t width, int3
 uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Bool coder: token streams (and raw bools) -> VP9 arithmetic-coded bytes.
+ *
+ * Replaces pack_mb_tokens over vpx_write (VPX/vp9_bitstream.c:98-162, VPX/bitwriter.h:34-84) between eb_vp9_start_encode and
+ * eb_vp9_stop_encode (VPX/bitwriter.c): the bytes of one tile.  A stream is coded as (128, 0), its bools, 32 x (128, 0), plus one zero
+ * byte when the last byte looks like a superframe marker ((last & 0xe0) == 0xc0).
+ *
+ *   bool record   uint16_t, bit << 8 | prob, prob in 1 .. 255
+ *   token record  the tokeniser's uint32_t (above); its bools are node 0 (bit = token != EOB; left out when the record's band is not
+ *                 0 and the record in front of it in the segment is ZERO), node 1, node 2, the eb_vp9_coef_con_tree walk over
+ *                 pareto[probs[2] - 1], the category bits MSB first, the sign at probability 128 -- 22 bools at most
+ *   segment       {first, count, kind}: kind 0 = `count` token records from d_tokens + first, kind 1 = `count` bool records from
+ *                 d_bools + first.  Segments are coded in list order; a transform block never straddles two segments.
+ * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
+ * uploaded once per context. */
+typedef struct svt_bool_tables {
+    uint8_t coef_probs[576 * 3]; /* [prob_row][node]: cm->fc->coef_probs flattened */
+    uint8_t pareto[255][8];      /* eb_vp9_pareto8_full */
+    uint8_t cat_probs[6][14];    /* eb_vp9_extra_bits[CATEGORY1_TOKEN + i].prob (8-bit depth), unused entries 0 */
+} svt_bool_tables;
+typedef struct svt_bool_segment {
+    uint32_t first, count, kind;
+} svt_bool_segment;
+#define SVT_BOOL_RECORD(bit, prob) ((uint16_t)((bit) << 8 | (prob)))
+#define SVT_BOOL_MAX_PER_TOKEN 22
+#define SVT_BOOL_SIZE_OVERFLOW 0xFFFFFFFFu
+/* one stream of a batch; every pointer is a device pointer.
+ *   d_segments  NULL: the stream is the token records d_tokens[0 .. n_tokens) (or *d_n_tokens of them when d_n_tokens is set, e.g.
+ *               the last entry of the tokeniser's d_sb_off: a count only the device knows)
+ *   max_bools   what the context's scratch is sized for (its kernels' grids as well): an upper bound of the stream's bools, e.g.
+ *               svt_hip_boolcode_bools_capacity(tokens).  A stream with more bools is not coded: *d_size = SVT_BOOL_SIZE_OVERFLOW;
+ *               the same answer for a stream with a non-empty segment of an unknown kind or of a kind whose buffer pointer is NULL
+ *               (the list lives on the device: the entry point cannot look at it)
+ *   d_size      WRITTEN always: the stream's size in bytes, also when it exceeds capacity -- nothing is then written at or beyond
+ *               d_bytes + capacity and the contents are unspecified */
+typedef struct svt_bool_stream {
+    const uint32_t         *d_tokens;
+    const uint16_t         *d_bools;
+    const svt_bool_segment *d_segments;
+    const uint32_t         *d_n_tokens;
+    uint32_t                n_segments, n_tokens, max_bools, capacity;
+    uint8_t                *d_bytes;
+    uint32_t               *d_size;
+} svt_bool_stream;
+#define SVT_BOOL_MAX_STREAMS 32
+
+int32_t svt_hip_boolcode_set_tables(svt_hip_ctx *ctx, const svt_bool_tables *tables);
+/* n_streams (<= SVT_BOOL_MAX_STREAMS) streams in one call (host array of descriptors holding device pointers).  Asynchronous on the
+ * context's stream: behind svt_hip_tokenize_batch_device on the same context it needs no host round trip.  Bit positions are 32-bit:
+ * a stream with 7 * (max_bools + 33) >= 2^32 is refused. */
+int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams);
+/* host-pointer convenience form of one stream (segments NULL: all n_tokens records); *size as d_size above */
+int32_t svt_hip_boolcode(svt_hip_ctx *ctx, const uint32_t *tokens, uint32_t n_tokens, const uint16_t *bools, uint32_t n_bools,
+                         const svt_bool_segment *segments, uint32_t n_segments, uint8_t *bytes, uint32_t capacity, uint32_t *size);
+/* the same rules (csrc/boolcode_core.h) in front of the plain serial writer, pure CPU, host pointers */
+int32_t svt_hip_boolcode_host(const svt_bool_tables *tables, const uint32_t *tokens, uint32_t n_tokens, const uint16_t *bools, uint32_t n_bools,
+                              const svt_bool_segment *segments, uint32_t n_segments, uint8_t *bytes, uint32_t capacity, uint32_t *size);
+/* bytes n_bools bools occupy at most (7 bits a bool, the 33 framing bools, the marker byte); bools n_tokens records expand to at most */
+uint32_t svt_hip_boolcode_capacity(uint32_t n_bools);
+uint32_t svt_hip_boolcode_bools_capacity(uint32_t n_tokens);
+/* the kernels' constants: bools per chunk (K) and chunks per tile of the chain kernel */
+void svt_hip_boolcode_geometry(int32_t *bools_per_chunk, int32_t *chunks_per_tile);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.
  *
  * Replaces, per batch of mutually independent pictures (e.g. the pictures of one temporal layer of a mini-GOP), the data path of

@@ -155,6 +155,20 @@ class TokPicture(C.Structure):
 TOK_COUNTS = 6912
 TOK_NONE = 0xFFFFFFFF
 
+
+# bool coder (svt_bool_tables / svt_bool_segment / svt_bool_stream of include/svtvp9_hip.h)
+BOOL_TABLES_DTYPE = np.dtype([("coef_probs", "u1", (576 * 3,)), ("pareto", "u1", (255, 8)), ("cat_probs", "u1", (6, 14))])
+assert BOOL_TABLES_DTYPE.itemsize == 576 * 3 + 255 * 8 + 6 * 14
+BOOL_SEGMENT_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("kind", "<u4")])
+BOOL_MAX_PER_TOKEN = 22
+BOOL_SIZE_OVERFLOW = 0xFFFFFFFF
+BOOL_MAX_STREAMS = 32
+
+
+class BoolStream(C.Structure):
+    _fields_ = [("d_tokens", C.c_void_p), ("d_bools", C.c_void_p), ("d_segments", C.c_void_p), ("d_n_tokens", C.c_void_p), ("n_segments", C.c_uint32),
+                ("n_tokens", C.c_uint32), ("max_bools", C.c_uint32), ("capacity", C.c_uint32), ("d_bytes", C.c_void_p), ("d_size", C.c_void_p)]
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -185,6 +199,8 @@ EXPORTS = [
     "svt_hip_pa_noise_params_derive", "svt_hip_pa_noise_batch_device", "svt_hip_pa_histogram_batch_device", "svt_hip_pa_chroma_mean_batch_device",
     "svt_hip_vp9_scan_tables", "svt_hip_tokenize_blocks_device", "svt_hip_tokenize_blocks", "svt_hip_tokenize_blocks_host", "svt_hip_tokenize_batch_device", "svt_hip_tokenize_picture",
     "svt_hip_tokenize_capacity",
+    "svt_hip_boolcode_set_tables", "svt_hip_boolcode_batch_device", "svt_hip_boolcode", "svt_hip_boolcode_host", "svt_hip_boolcode_capacity", "svt_hip_boolcode_bools_capacity",
+    "svt_hip_boolcode_geometry",
 ]
 
 _lib = None
@@ -215,6 +231,14 @@ def load():
         _lib.svt_hip_vp9_scan_tables.restype = C.POINTER(C.c_int16)
         _lib.svt_hip_vp9_scan_tables.argtypes = [C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_int32)]
         _lib.svt_hip_tokenize_capacity.restype = C.c_uint32
+        _lib.svt_hip_boolcode_capacity.restype = C.c_uint32
+        _lib.svt_hip_boolcode_capacity.argtypes = [C.c_uint32]
+        _lib.svt_hip_boolcode_bools_capacity.restype = C.c_uint32
+        _lib.svt_hip_boolcode_bools_capacity.argtypes = [C.c_uint32]
+        _lib.svt_hip_boolcode_geometry.restype = None
+        _u32 = C.c_uint32
+        _lib.svt_hip_boolcode_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.POINTER(_u32)]
+        _lib.svt_hip_boolcode.argtypes = [C.c_void_p] + _lib.svt_hip_boolcode_host.argtypes[1:]
         _lib.svt_hip_encdec_work_destroy.restype = None
         _lib.svt_hip_host_free.restype = None
         _lib.svt_hip_encdec_work_set_stage_hook.restype = None

@@ -1,0 +1,46 @@
+/*
+ * A stand-in for <hip/hip_runtime.h> that lets csrc/boolcode.hip compile as plain C++ and run on the CPU (tests/test_boolcode_emu.py):
+ * one thread per lane of a workgroup, a pthread barrier for __syncthreads, wave shuffles through a shared array (every call site of
+ * the bool coder's kernels is workgroup-uniform), __shared__ as a static (one workgroup runs at a time), device memory = host memory.
+ * Only what boolcode.hip and svt_ctx.h use is here.
+ */
+#pragma once
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <pthread.h>
+#include <vector>
+#include <thread>
+#include <functional>
+#define __global__
+#define __device__
+#define __host__
+#define __forceinline__ inline
+#define __launch_bounds__(x)
+#define __shared__ static
+struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
+struct uint4 { uint32_t x, y, z, w; };
+extern thread_local dim3 threadIdx, blockIdx, blockDim;
+extern pthread_barrier_t *g_bar;
+extern unsigned long long g_shfl[1024];
+inline void __syncthreads() { pthread_barrier_wait(g_bar); }
+template <typename T> inline T __shfl_up(T v, int d, int w) {
+    g_shfl[threadIdx.x] = (unsigned long long)v;
+    __syncthreads();
+    T r = ((int)(threadIdx.x & 63) >= d) ? (T)g_shfl[threadIdx.x - d] : v;
+    __syncthreads();
+    return r;
+}
+inline int __builtin_amdgcn_readfirstlane(int v) { return v; }
+inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+typedef int hipError_t; typedef void *hipStream_t; typedef void *hipEvent_t;
+enum { hipSuccess = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
+inline hipError_t hipSetDevice(int) { return 0; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
+inline hipError_t hipGetLastError() { return 0; }
+inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int, hipStream_t) { memcpy(d, s, n); return 0; }
+inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n + 64); memset(*p, 0xCD, n + 64); return 0; }
+inline hipError_t hipFree(void *p) { free(p); return 0; }
+void emu_launch(dim3 grid, dim3 block, std::function<void()> body);
+#define hipLaunchKernelGGL(kernel, grid, block, shm, stream, ...) emu_launch(grid, block, [=] { kernel(__VA_ARGS__); })
