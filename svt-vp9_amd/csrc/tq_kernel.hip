@@ -15,11 +15,52 @@
  * Source, prediction and reconstruction move as dword rows (lane i owns row i); the row <-> column changes go through the
  * same LDS tile; coefficient rows leave as 8/16-byte vectors (coeff_off and the two coefficient arrays must be 16-byte
  * aligned: every block starts on a multiple of 8 coefficients).  Global traffic per block: N*N source + N*N prediction bytes in, 2*N*N int16 (qcoeff, dqcoeff) + N*N recon out.
+ *
+ * The walks.  Every launch is persistent: a workgroup walks groups of blocks (256 4x4 blocks, 256 / N blocks otherwise) of its XCD's
+ * eighth of the list (tq_walk_of).  An iteration needs the block's position code (or descriptor), from it the picture's geometry
+ * record, from that the 2 N rows of source and prediction: three dependent round trips, two of them to lines nobody has touched, in
+ * front of ~500 (4x4) / ~700 (8x8) vector instructions.  The 4x4 and 8x8 instances without the fused rate pass walk software-pipelined
+ * (tq_pipelined): after a prologue that fetches the first group, an iteration
+ *     loads both descriptors -- its own group's, whole, and the address fields of the next group's -- and waits for them (lines the
+ *         previous iteration has just read: one short round trip),
+ *     issues the row loads of group gj + step and the position-code load of group gj + 2 step, waits for neither,
+ *     runs the body of group gj on the rows the previous iteration fetched (tq_block_body / tq_lane_block take them as arguments),
+ *     and moves the fetched registers down.
+ * The prefetch is predicated like the loop: no load is issued for a group at or beyond n_blocks (the list's tail need not be readable),
+ * and the idle slots of a partly filled last group work on block 0 and store nothing, as before.  The wait in the first step is
+ * explicit (tq_loads_landed): loads return in order, so a wait that the compiler places behind the far loads for one of the near ones
+ * would wait for the far ones too.  What it costs: 14 - 16 registers (4x4: 63 -> 77, 8x8: 62 -> 78; both were in the 64-register
+ * class, both are now in the 80-register one), no scratch.  The 16x16 instance would need 108 (> 96: one wave per SIMD less) and the
+ * 32x32 one sits at 128 with scalar spills: both keep the serial walk, as do the instances with the fused rate pass (the 4x4 one: 129
+ * registers pipelined instead of 113, a wave per SIMD less).
+ *
+ * The grids.  In the encode pass the launches run beside motion estimation, whose five workgroups per CU leave 112 registers per SIMD
+ * and 3 LDS granules: a CU on which more than that moves in loses ME workgroups for as long as it stays.  The mode-decision
+ * entry points keep six workgroups per CU (TQ_PER_2CU); svt_tq_launch_device_lists launches TQ_PER_2CU_ENC per size, chosen from a sweep
+ * of the bench step (profiles/tq_prefetch.md):
+ *     4x4: one workgroup on every other CU (128 on this part).  One wave of 80 registers and no LDS per SIMD is the only form of this
+ *         stage that fits beside FIVE ME workgroups, and the step is fastest there: 6 465 frames/s for the parent, 6 740 at 128
+ *         workgroups, 6 610 - 6 735 at 192 - 384, 6 515 at 1 536; below 128 the launch itself becomes the chain's long pole (64: 6 665,
+ *         32: 5 640).  The same grid under the serial loop gives 6 690: most of the gain is the grid, the prefetch adds what lets
+ *         so few waves keep up.
+ *     8x8, 16x16, 32x32: two workgroups per CU.  Their LDS tiles (8 / 14 / 27 granules) cost a CU one ME workgroup whatever the
+ *         count; between one and six per CU the step moves by less than its run-to-run spread, except 32x32 at one on every other CU
+ *         (-1.3 %) and all three at six per CU together (-1.7 %).
  */
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "tq_core.h"
 
 namespace {
+
+/* The pipelined walks put this between the loads of the descriptors and the loads they send ahead for later groups.  Loads return in
+ * order: a wait for an older load that the compiler places AFTER the younger, far ones have been issued waits for those too -- and where
+ * two paths meet it has to place the wait that is safe on both.  With the descriptors landed here, the first thing a block body waits for
+ * is a table load of its own, two transform passes later. */
+__device__ __forceinline__ void tq_loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0); expcnt, lgkmcnt untouched */ }
+
+/* which instances walk their list software-pipelined (file comment) */
+template <int N, bool RATE, bool DIST> constexpr bool tq_pipelined() { return N < 16 && !RATE; }
 
 /* 32x32: 54 KB of LDS per 256-thread workgroup (eight blocks + the rate tables) allow three workgroups = 12 waves per CU */
 template <int N, bool RATE, bool DIST>
@@ -60,34 +101,96 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? (
     const int lb  = threadIdx.x / N;      /* block slot inside the workgroup */
     const int i   = threadIdx.x % N;      /* column (pass 1) / row (pass 2) owned by this lane */
     const tq_walk wk = tq_walk_of((n_blocks + BPW - 1) / BPW);
-  for (int gj = wk.first; gj < wk.per_xcd; gj += wk.step) {
-    const int grp = wk.base + gj;
-    if (grp * BPW >= n_blocks) break;     /* uniform: depends on the workgroup only */
-    const int blk = grp * BPW + lb;
-    const bool active = blk < n_blocks;
-    svt_tq_block k;
-    if (dc.pos) { /* (uniform) the list holds position codes: the descriptor is rebuilt in registers */
-        const uint32_t pc = dc.pos[active ? blk : 0];
-        svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
-    } else if (active) k = blocks[blk];
-    else { k = blocks[0]; }
-    int32_t *t = tile[lb];
-    /* lane i fetches ROW i of source and prediction as dwords (coalesced: the N lanes of a block read N consecutive rows of N bytes) */
-    uint32_t srow[N / 4], prow[N / 4];
-    {
+    /* group gj of this workgroup's walk exists (uniform: depends on the workgroup only; once false it stays false) */
+    auto in_walk = [&](int gj) { return gj < wk.per_xcd && (wk.base + gj) * BPW < n_blocks; };
+    /* the lane's block of group gj; the idle slots of a partly filled last group work on block 0 and store nothing */
+    auto code_of = [&](int gj) { const int blk = (wk.base + gj) * BPW + lb; return dc.pos[blk < n_blocks ? blk : 0]; };
+    /* POS (dc.pos != null): the list holds position codes and the descriptor is rebuilt in registers */
+    auto block_of = [&](auto POS, int gj, uint32_t pc, svt_tq_block &k) {
+        const int blk = (wk.base + gj) * BPW + lb;
+        if constexpr (decltype(POS)::value)
+            svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+        else k = blocks[blk < n_blocks ? blk : 0];
+    };
+    /* lane i fetches ROW i of source and prediction as dwords (coalesced: the N lanes of a block read N consecutive rows of N bytes);
+     * of the descriptor only the address fields are used */
+    auto rows_of = [&](int gj, const svt_tq_block &k, uint32_t (&srow)[N / 4], uint32_t (&prow)[N / 4]) {
+        _Pragma("unroll") for (int q = 0; q < N / 4; q++) { srow[q] = 0u; prow[q] = 0u; }
+        if ((wk.base + gj) * BPW + lb >= n_blocks) return;
         const uint8_t *sp = src + k.src_off + (size_t)i * k.src_stride;
         const uint8_t *pp = pred + k.pred_off + (size_t)i * k.pred_stride;
         constexpr uintptr_t AM = N >= 16 ? 15 : N - 1;
-        _Pragma("unroll") for (int q = 0; q < N / 4; q++) { srow[q] = 0u; prow[q] = 0u; }
-        if (active) { row_load<N>(sp, ((uintptr_t)sp & AM) == 0, srow); row_load<N>(pp, ((uintptr_t)pp & AM) == 0, prow); }
+        row_load<N>(sp, ((uintptr_t)sp & AM) == 0, srow); row_load<N>(pp, ((uintptr_t)pp & AM) == 0, prow);
+    };
+    auto body_of = [&](int gj, const svt_tq_block &k, const uint32_t (&srow)[N / 4], const uint32_t (&prow)[N / 4]) {
+        const int  blk = (wk.base + gj) * BPW + lb;
+        const bool active = blk < n_blocks;
+        /* a batch may reconstruct into several buffers (reference pictures of different mini-GOPs): pad_[0] bits 4-6 name the one */
+        int32_t *bits_slot = nullptr;
+        if constexpr (RATE) bits_slot = ra.bits + blk;
+        tq_block_body<N, RATE, DIST>(k, active, i, tile[lb], srow, prow, qtabs, iscan_all, qcoeff, dqcoeff, eob_out + blk, dist_out ? dist_out + 2 * blk : nullptr, bits_slot,
+                                     ra.T, s_tc, s_scan, recon_set ? (uint8_t *)recon_set[(k.pad_[0] >> 4) & 7] : recon);
+        tq_block_sync(); /* the block's tile is rewritten by its lanes' next block */
+    };
+    int gj = wk.first;
+    if constexpr (!tq_pipelined<N, RATE, DIST>()) { /* the serial walk: fetch, then compute (spelled out: written with the helpers above the
+                                                     * 32x32 instance gets a vector spill) */
+        for (; gj < wk.per_xcd; gj += wk.step) {
+            const int grp = wk.base + gj;
+            if (grp * BPW >= n_blocks) break;     /* uniform: depends on the workgroup only */
+            const int blk = grp * BPW + lb;
+            const bool active = blk < n_blocks;
+            svt_tq_block k;
+            if (dc.pos) { /* (uniform) the list holds position codes: the descriptor is rebuilt in registers */
+                const uint32_t pc = dc.pos[active ? blk : 0];
+                svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+            } else if (active) k = blocks[blk];
+            else { k = blocks[0]; }
+            int32_t *t = tile[lb];
+            uint32_t srow[N / 4], prow[N / 4];
+            {
+                const uint8_t *sp = src + k.src_off + (size_t)i * k.src_stride;
+                const uint8_t *pp = pred + k.pred_off + (size_t)i * k.pred_stride;
+                constexpr uintptr_t AM = N >= 16 ? 15 : N - 1;
+                _Pragma("unroll") for (int q = 0; q < N / 4; q++) { srow[q] = 0u; prow[q] = 0u; }
+                if (active) { row_load<N>(sp, ((uintptr_t)sp & AM) == 0, srow); row_load<N>(pp, ((uintptr_t)pp & AM) == 0, prow); }
+            }
+            int32_t *bits_slot = nullptr;
+            if constexpr (RATE) bits_slot = ra.bits + blk;
+            tq_block_body<N, RATE, DIST>(k, active, i, t, srow, prow, qtabs, iscan_all, qcoeff, dqcoeff, eob_out + blk, dist_out ? dist_out + 2 * blk : nullptr, bits_slot,
+                                         ra.T, s_tc, s_scan, recon_set ? (uint8_t *)recon_set[(k.pad_[0] >> 4) & 7] : recon);
+            tq_block_sync(); /* the block's tile is rewritten by its lanes' next block */
+        }
+    } else {
+        /* software-pipelined walk (file comment): while group gj computes, the rows of group gj + step and the position codes of
+         * group gj + 2 step are in flight.  Nothing is loaded for a group that is not in the walk.  One copy of the loop per list form,
+         * so that the loads of an iteration's descriptors sit in one basic block and are waited for once. */
+        auto walk = [&](auto POS) {
+            constexpr bool P = decltype(POS)::value;
+            bool     have0 = in_walk(gj), have1 = have0 && in_walk(gj + wk.step);
+            uint32_t pc0 = 0u, pc1 = 0u, s0[N / 4], p0[N / 4];
+            if constexpr (P) { if (have0) pc0 = code_of(gj); if (have1) pc1 = code_of(gj + wk.step); }
+            if (have0) { svt_tq_block k; block_of(POS, gj, pc0, k); rows_of(gj, k, s0, p0); }
+            while (have0) {
+                const int  g1 = gj + wk.step, g2 = g1 + wk.step;
+                const bool have2 = have1 && in_walk(g2);
+                uint32_t   pc2 = 0u, s1[N / 4], p1[N / 4];
+                /* both descriptors first: this group's, whole, and the address fields of the next one's (this group's again when
+                 * there is no next) -- lines that the previous iteration or a neighbour has just read */
+                svt_tq_block k, kn;
+                block_of(POS, gj, pc0, k);
+                block_of(POS, have1 ? g1 : gj, have1 ? pc1 : pc0, kn);
+                tq_loads_landed();
+                if (have1) rows_of(g1, kn, s1, p1);
+                else { _Pragma("unroll") for (int q = 0; q < N / 4; q++) { s1[q] = 0u; p1[q] = 0u; } }
+                if constexpr (P) { if (have2) pc2 = code_of(g2); }
+                body_of(gj, k, s0, p0);
+                _Pragma("unroll") for (int q = 0; q < N / 4; q++) { s0[q] = s1[q]; p0[q] = p1[q]; }
+                pc0 = pc1; pc1 = pc2; gj = g1; have0 = have1; have1 = have2;
+            }
+        };
+        if (dc.pos) walk(std::true_type{}); else walk(std::false_type{});
     }
-    /* a batch may reconstruct into several buffers (reference pictures of different mini-GOPs): pad_[0] bits 4-6 name the one */
-    int32_t *bits_slot = nullptr;
-    if constexpr (RATE) bits_slot = ra.bits + blk;
-    tq_block_body<N, RATE, DIST>(k, active, i, t, srow, prow, qtabs, iscan_all, qcoeff, dqcoeff, eob_out + blk, dist_out ? dist_out + 2 * blk : nullptr, bits_slot,
-                                 ra.T, s_tc, s_scan, recon_set ? (uint8_t *)recon_set[(k.pad_[0] >> 4) & 7] : recon);
-    tq_block_sync(); /* the block's tile is rewritten by its lanes' next block */
-  }
 }
 
 
@@ -133,9 +236,22 @@ __device__ __forceinline__ int rate_walk4(const int (&tok)[16], const int (&en)[
  * 8x8: they differ in the cast inside tx_fdct8 (vp9_dct.c:67-68), selected by the block's transform type.  The inverse
  * always runs all rows (the reference's reduced variants are shortcuts with identical results).  Memory instructions per
  * block are unchanged (a lane issues the N row loads its N lanes issued). */
-/* one 4x4 (8x8) block, whole, in the calling lane: the body of svt_tq_lane_kernel */
+/* the N rows of source and prediction of a block, packed, into the calling lane */
+template <int N>
+__device__ __forceinline__ void tq_lane_rows(const svt_tq_block &k, const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, uint32_t (&srow)[N][N / 4], uint32_t (&prow)[N][N / 4]) {
+    _Pragma("unroll") for (int r = 0; r < N; r++) {
+        const uint8_t *sp = src + k.src_off + (size_t)r * k.src_stride, *pp = pred + k.pred_off + (size_t)r * k.pred_stride;
+        if constexpr (N == 4) { srow[r][0] = *(const uint32_t *)sp; prow[r][0] = *(const uint32_t *)pp; }
+        else {
+            row_load<N>(sp, ((uintptr_t)sp & 7) == 0, srow[r]);
+            row_load<N>(pp, ((uintptr_t)pp & 7) == 0, prow[r]);
+        }
+    }
+}
+
+/* one 4x4 (8x8) block, whole, in the calling lane: the body of svt_tq_lane_kernel.  srow / prow: its rows (tq_lane_rows) */
 template <int N, bool RATE, bool DIST>
-__device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int blk, const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, uint8_t *__restrict__ recon,
+__device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int blk, const uint32_t (&srow)[N][N / 4], const uint32_t (&prow)[N][N / 4], uint8_t *__restrict__ recon,
                                               const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all, int16_t *__restrict__ qcoeff,
                                               int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out, uint64_t *__restrict__ dist_out, const tq_rate_args &ra,
                                               const uint32_t *s_tc, const int32_t *s_vc, const uint8_t *const *__restrict__ recon_set) {
@@ -143,18 +259,8 @@ __device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int b
     const bool col_adst = k.tx_type == SVT_ADST_DCT || k.tx_type == SVT_ADST_ADST;
     const bool row_adst = k.tx_type == SVT_DCT_ADST || k.tx_type == SVT_ADST_ADST;
     const bool dct_dct  = k.tx_type == SVT_DCT_DCT;
-    uint32_t   prow[N][ND];
     int32_t    m[N][N]; /* after the column pass: m[kk][cc] = vertical frequency kk of column cc */
     {
-        uint32_t srow[N][ND];
-        _Pragma("unroll") for (int r = 0; r < N; r++) {
-            const uint8_t *sp = src + k.src_off + (size_t)r * k.src_stride, *pp = pred + k.pred_off + (size_t)r * k.pred_stride;
-            if constexpr (N == 4) { srow[r][0] = *(const uint32_t *)sp; prow[r][0] = *(const uint32_t *)pp; }
-            else {
-                row_load<N>(sp, ((uintptr_t)sp & 7) == 0, srow[r]);
-                row_load<N>(pp, ((uintptr_t)pp & 7) == 0, prow[r]);
-            }
-        }
         _Pragma("unroll") for (int cc = 0; cc < N; cc++) {
             int32_t v[N], o[N];
             _Pragma("unroll") for (int r = 0; r < N; r++)
@@ -327,39 +433,89 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
         __syncthreads();
     }
     const tq_walk wk = tq_walk_of((n_blocks + 255) / 256);
-  for (int gj = wk.first; gj < wk.per_xcd; gj += wk.step) {
-    const int blk = (wk.base + gj) * 256 + (int)threadIdx.x;
-    if (blk >= n_blocks) continue; /* no barrier inside the loop */
-    svt_tq_block k;
-    if (dc.pos) {
-        const uint32_t pc = dc.pos[blk];
-        svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
-    } else k = blocks[blk];
-    tq_lane_block<N, RATE, DIST>(k, blk, src, pred, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
-  }
+    /* Software-pipelined walk (file comment), per lane: while the lane's block of group gj computes, the rows of its block of group
+     * gj + step and the position code of its block of group gj + 2 step are in flight.  A lane loads nothing for a block at or beyond
+     * n_blocks (once a lane is past the end it stays there); no barrier inside the loop. */
+    auto blk_of = [&](int gj) { return (wk.base + gj) * 256 + (int)threadIdx.x; };
+    auto in_walk = [&](int gj) { return gj < wk.per_xcd && blk_of(gj) < n_blocks; };
+    auto block_of = [&](auto POS, int gj, uint32_t pc, svt_tq_block &k) {
+        if constexpr (decltype(POS)::value) svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+        else k = blocks[blk_of(gj)];
+    };
+    if constexpr (!tq_pipelined<N, RATE, DIST>()) { /* the serial walk: fetch, then compute */
+      for (int gj = wk.first; gj < wk.per_xcd; gj += wk.step) {
+        const int blk = (wk.base + gj) * 256 + (int)threadIdx.x;
+        if (blk >= n_blocks) continue; /* no barrier inside the loop */
+        svt_tq_block k;
+        if (dc.pos) {
+            const uint32_t pc = dc.pos[blk];
+            svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+        } else k = blocks[blk];
+        uint32_t srow[N][N / 4], prow[N][N / 4];
+        tq_lane_rows<N>(k, src, pred, srow, prow);
+        tq_lane_block<N, RATE, DIST>(k, blk, srow, prow, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
+      }
+      return;
+    }
+    auto walk = [&](auto POS) { /* one copy per list form (svt_tq_kernel) */
+        constexpr bool P = decltype(POS)::value;
+        int      gj = wk.first;
+        bool     have0 = in_walk(gj), have1 = have0 && in_walk(gj + wk.step);
+        uint32_t pc0 = 0u, pc1 = 0u, s0[N][N / 4] = {}, p0[N][N / 4] = {};
+        if constexpr (P) { if (have0) pc0 = dc.pos[blk_of(gj)]; if (have1) pc1 = dc.pos[blk_of(gj + wk.step)]; }
+        if (have0) { svt_tq_block k; block_of(POS, gj, pc0, k); tq_lane_rows<N>(k, src, pred, s0, p0); }
+        while (have0) {
+            const int  g1 = gj + wk.step, g2 = g1 + wk.step;
+            const bool have2 = have1 && in_walk(g2);
+            uint32_t   pc2 = 0u, s1[N][N / 4] = {}, p1[N][N / 4] = {};
+            svt_tq_block k, kn; /* this block's descriptor, whole, and the address fields of the lane's next (svt_tq_kernel) */
+            block_of(POS, gj, pc0, k);
+            block_of(POS, have1 ? g1 : gj, have1 ? pc1 : pc0, kn);
+            tq_loads_landed();
+            if (have1) tq_lane_rows<N>(kn, src, pred, s1, p1);
+            if constexpr (P) { if (have2) pc2 = dc.pos[blk_of(g2)]; }
+            tq_lane_block<N, RATE, DIST>(k, blk_of(gj), s0, p0, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
+            _Pragma("unroll") for (int r = 0; r < N; r++) { _Pragma("unroll") for (int q = 0; q < N / 4; q++) { s0[r][q] = s1[r][q]; p0[r][q] = p1[r][q]; } }
+            pc0 = pc1; pc1 = pc2; gj = g1; have0 = have1; have1 = have2;
+        }
+    };
+    if (dc.pos) walk(std::true_type{}); else walk(std::false_type{});
 }
 
-/* persistent grid: a multiple of 8 workgroups (one walk per XCD, tq_walk_of), at most `per_cu` per compute unit */
-int tq_grid(svt_hip_ctx *ctx, int ngroups, int per_cu) {
-    const int per_xcd = (ngroups + 7) / 8, cap = (ctx->cu_count * per_cu + 7) / 8;
+/* persistent grid: a multiple of 8 workgroups (one walk per XCD, tq_walk_of), at most `per_2cu` per pair of compute units.
+ * SVT_HIP_TQ_GRID=a,b,c,d (an experiment aid, read once): the largest grid of a 4x4 / 8x8 / 16x16 / 32x32 launch in workgroups, rounded up
+ * to a multiple of 8; 0 or absent = the built-in cap.  It is how the caps below were swept, and how a small batch gets long walks. */
+int tq_grid(svt_hip_ctx *ctx, int ngroups, int per_2cu, int size) {
+    static const struct grid_env { int v[4]; } env = [] {
+        grid_env g = {{0, 0, 0, 0}};
+        if (const char *e = getenv("SVT_HIP_TQ_GRID")) sscanf(e, "%d,%d,%d,%d", &g.v[0], &g.v[1], &g.v[2], &g.v[3]);
+        return g;
+    }();
+    const int per_xcd = (ngroups + 7) / 8, cap = env.v[size] > 0 ? (env.v[size] + 7) / 8 : (ctx->cu_count * per_2cu + 15) / 16;
     return 8 * (per_xcd < cap ? per_xcd : cap);
 }
+
+/* workgroups per two CUs of a mode-decision launch (svt_hip_tq_*batch*: six per CU; nothing is known about what runs beside it) */
+constexpr int TQ_PER_2CU = 12;
+/* ... and of an encode-pass launch (svt_tq_launch_device_lists) per size: one 4x4 workgroup on every other CU, two per CU of the others
+ * (file comment, profiles/tq_prefetch.md) */
+constexpr int TQ_PER_2CU_ENC[4] = {1, 4, 4, 4};
 
 template <int N, bool RATE, bool DIST = true>
 hipError_t launch_tq(svt_hip_ctx *ctx, const uint8_t *src, const uint8_t *pred, uint8_t *recon, const svt_tq_block *blocks, int n,
                      const svt_quant_tables *q, const int16_t *iscan, int16_t *qc, int16_t *dqc, uint16_t *eob, uint64_t *dist, tq_rate_args ra,
-                     const uint8_t *const *recon_set, tq_dev_count dc = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0}) {
+                     const uint8_t *const *recon_set, tq_dev_count dc = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0}, int per_2cu = TQ_PER_2CU) {
     if (n <= 0) return hipSuccess;
     /* block per lane for 4x4 only: the 8x8 instance is bit-exact too but needs 201 VGPRs (64 samples + the transposed
      * intermediate live in one lane; 87 spills when held to 128) -- two waves per SIMD, and each displaces two ME waves:
      * the overlapped step went from 3.27 to 3.77 ms with it, so 8x8 stays on the N-lanes-per-block kernel */
     if constexpr (N == 4) {
-        hipLaunchKernelGGL((svt_tq_lane_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + 255) / 256, 6)), dim3(256), 0, ctx->stream, src, pred, recon, blocks, n, q,
+        hipLaunchKernelGGL((svt_tq_lane_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + 255) / 256, per_2cu, 0)), dim3(256), 0, ctx->stream, src, pred, recon, blocks, n, q,
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     } else {
         constexpr int NT = tq_threads<N, RATE>(), BPW = NT / N;
-        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, 6)), dim3(NT), 0, ctx->stream, src, pred, recon, blocks, n, q,
+        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, per_2cu, txcfg<N>::size)), dim3(NT), 0, ctx->stream, src, pred, recon, blocks, n, q,
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     }
@@ -414,7 +570,7 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
     const uint8_t *const *d_set = (const uint8_t *const *)d;
     const tq_rate_args none = {nullptr, nullptr, nullptr};
     hipError_t rc = hipSuccess;
-#define TQ_DEV(N, S, D) launch_tq<N, false, D>(ctx, d_src, d_pred, nullptr, d_blocks, cap[S], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob, d_dist, none, d_set, tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols})
+#define TQ_DEV(N, S, D) launch_tq<N, false, D>(ctx, d_src, d_pred, nullptr, d_blocks, cap[S], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob, d_dist, none, d_set, tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols}, TQ_PER_2CU_ENC[S])
     if (d_dist) { /* with the coefficient-domain distortion pair */
         rc = TQ_DEV(4, 0, true);
         if (rc == hipSuccess) rc = TQ_DEV(8, 1, true);
