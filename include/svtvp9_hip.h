@@ -823,7 +823,8 @@ uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
  *   segment       {first, count, kind}: kind 0 = `count` token records from d_tokens + first, kind 1 = `count` bool records from
  *                 d_bools + first.  Segments are coded in list order; a transform block never straddles two segments.
  * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
- * uploaded once per context. */
+ * uploaded once per context.  The raw bools and the segment list of a key frame's tile come from the mode-info stage below; inter
+ * pictures' mode info, the uncompressed and compressed headers and packet delivery are not on the device. */
 typedef struct svt_bool_tables {
     uint8_t coef_probs[576 * 3]; /* [prob_row][node]: cm->fc->coef_probs flattened */
     uint8_t pareto[255][8];      /* eb_vp9_pareto8_full */
@@ -871,6 +872,60 @@ uint32_t svt_hip_boolcode_capacity(uint32_t n_bools);
 uint32_t svt_hip_boolcode_bools_capacity(uint32_t n_tokens);
 /* the kernels' constants: bools per chunk (K) and chunks per tile of the chain kernel */
 void svt_hip_boolcode_geometry(int32_t *bools_per_chunk, int32_t *chunks_per_tile);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Key-frame mode-info syntax: the grid of an intra-only picture -> the raw bools and the segment list that, with the tokeniser's
+ * records, make the bool coder write the complete compressed tile data of the picture.
+ *
+ * Replaces, for intra-only pictures, what eb_vp9_entropy_coding_kernel codes per block in front of its tokens
+ * (Codec/EbEntropyCodingProcess.c:110-442): write_partition (VPX/vp9_bitstream.c:399-417) at every node of an SB's quad-tree that
+ * reaches into the picture and write_mb_modes_kf (:323-358) at every leaf -- skip, luma mode(s), chroma mode; no transform size
+ * (tx_mode is ALLOW_32X32) and no segment id.  Every context is read from the grid (csrc/modeinfo_core.h says why that is the serial
+ * walk's value).  Chain: intra encode pass -> tokeniser -> this -> bool coder, all on one context's stream, no host round trip; the
+ * result is what the reference writes between eb_vp9_start_encode and eb_vp9_stop_encode.
+ *
+ * The tables are the caller's data (VPX/vp9_entropymode.c: eb_vp9_kf_y_mode_prob, eb_vp9_kf_uv_mode_prob, eb_vp9_kf_partition_probs;
+ * the frame's skip probabilities), uploaded once per context. */
+typedef struct svt_modes_tables {
+    uint8_t kf_y_mode_prob[10][10][9]; /* [above][left][node] */
+    uint8_t kf_uv_mode_prob[10][9];    /* [luma mode][node] */
+    uint8_t kf_partition_probs[16][3]; /* [4 * level (8x8 .. 64x64) + 2 * left + above][node] */
+    uint8_t skip_probs[3];             /* [above skip + left skip] */
+} svt_modes_tables;
+#define SVT_MODES_BAD_GRID 0xFFFFFFFFu
+/* one picture of a batch; every pointer is a device pointer (host pointers in the host form).
+ *   d_lf_mi     the grid as svt_hip_encdec_intra_device takes it (sb_type 0 / 3 / 6 / 9, modes in pad_[1], pad_[2] and the nibbles of
+ *               pad_[0]; `skip` as the encode pass wrote it), and also sb_type 12 with tx_size 3
+ *   d_eob_map, d_tok_off   the tokeniser's input and output: first token and token count of every leaf's Y, Cb and Cr runs
+ *   d_bools     WRITTEN: the picture's bool records in coding order; nothing is written at or beyond d_bools + capacity
+ *               (svt_hip_modes_bools_capacity always suffices).  4-byte aligned
+ *   d_segments  WRITTEN, every one of the svt_hip_modes_segments records: four per 8x8 unit, SBs raster, units in z-order --
+ *               {kind 1: the bools that start at the unit}, {kind 0: Y tokens}, {Cb}, {Cr}; count 0 where the unit is no leaf's origin,
+ *               lies outside the picture, or the leaf is skipped.  Handed to the bool coder with the tokeniser's d_tokens and d_bools
+ *               the list codes the tile.  16-byte aligned
+ *   d_n_bools   WRITTEN always: the picture's bools, also when they exceed capacity; SVT_MODES_BAD_GRID for a grid this entry does not
+ *               take (a rectangular sb_type, is_inter != 0, a mode above 9, a block that crosses the picture edge or overlaps another, a
+ *               tx_size other than the block's largest up to 32x32): every segment is then empty */
+typedef struct svt_modes_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const uint16_t         *d_eob_map;
+    const uint32_t         *d_tok_off;
+    uint16_t               *d_bools;
+    svt_bool_segment       *d_segments;
+    uint32_t               *d_n_bools;
+    uint32_t                capacity;   /* records d_bools can hold */
+    uint32_t                pad_;
+} svt_modes_picture;
+int32_t svt_hip_modes_set_tables(svt_hip_ctx *ctx, const svt_modes_tables *tables);
+/* n_pics (<= 32) pictures of one geometry in one call (host array of descriptors holding device pointers).  Asynchronous on the
+ * context's stream: behind svt_hip_tokenize_batch_device and in front of svt_hip_boolcode_batch_device it needs no host round trip. */
+int32_t svt_hip_modes_kf_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_modes_picture *pics, int32_t width, int32_t height, int32_t mi_stride);
+/* host form of the same text (csrc/modeinfo_core.h), pure CPU, host pointers; also checks the per-unit bound of the capacity */
+int32_t svt_hip_modes_kf_picture(const svt_modes_tables *tables, const svt_modes_picture *pic, int32_t width, int32_t height, int32_t mi_stride);
+/* records of a picture's segment list (a host value: svt_bool_stream.n_segments); bools a picture emits at most: its 8x8 units times
+ * 48 = 4 partition symbols of 3 bools + skip + (4 luma modes + the chroma mode) of 7 bools */
+uint32_t svt_hip_modes_segments(int32_t width, int32_t height);
+uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.

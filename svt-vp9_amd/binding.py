@@ -169,6 +169,18 @@ class BoolStream(C.Structure):
     _fields_ = [("d_tokens", C.c_void_p), ("d_bools", C.c_void_p), ("d_segments", C.c_void_p), ("d_n_tokens", C.c_void_p), ("n_segments", C.c_uint32),
                 ("n_tokens", C.c_uint32), ("max_bools", C.c_uint32), ("capacity", C.c_uint32), ("d_bytes", C.c_void_p), ("d_size", C.c_void_p)]
 
+
+# key-frame mode-info stage (svt_modes_tables / svt_modes_picture of include/svtvp9_hip.h)
+MODES_TABLES_DTYPE = np.dtype([("kf_y_mode_prob", "u1", (10, 10, 9)), ("kf_uv_mode_prob", "u1", (10, 9)), ("kf_partition_probs", "u1", (16, 3)), ("skip_probs", "u1", (3,))])
+assert MODES_TABLES_DTYPE.itemsize == 900 + 90 + 48 + 3
+MODES_BAD_GRID = 0xFFFFFFFF
+MODES_UNIT_BOOLS = 48
+
+
+class ModesPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_eob_map", C.c_void_p), ("d_tok_off", C.c_void_p), ("d_bools", C.c_void_p), ("d_segments", C.c_void_p),
+                ("d_n_bools", C.c_void_p), ("capacity", C.c_uint32), ("pad_", C.c_uint32)]
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -201,6 +213,7 @@ EXPORTS = [
     "svt_hip_tokenize_capacity",
     "svt_hip_boolcode_set_tables", "svt_hip_boolcode_batch_device", "svt_hip_boolcode", "svt_hip_boolcode_host", "svt_hip_boolcode_capacity", "svt_hip_boolcode_bools_capacity",
     "svt_hip_boolcode_geometry",
+    "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
 ]
 
 _lib = None
@@ -236,6 +249,8 @@ def load():
         _lib.svt_hip_boolcode_bools_capacity.restype = C.c_uint32
         _lib.svt_hip_boolcode_bools_capacity.argtypes = [C.c_uint32]
         _lib.svt_hip_boolcode_geometry.restype = None
+        _lib.svt_hip_modes_segments.restype = C.c_uint32
+        _lib.svt_hip_modes_bools_capacity.restype = C.c_uint32
         _u32 = C.c_uint32
         _lib.svt_hip_boolcode_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.POINTER(_u32)]
         _lib.svt_hip_boolcode.argtypes = [C.c_void_p] + _lib.svt_hip_boolcode_host.argtypes[1:]
