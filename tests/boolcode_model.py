@@ -273,6 +273,35 @@ def straddle_stream(n, seed, pad=0):
     return out, len(out) - 1
 
 
+# raw streams past one pass of the device's scan over tiles of 1024 items (256 tiles a pass): at the pass boundary and two passes + 5
+LONG_RAW = (256 * 1024 - 1, 256 * 1024, 256 * 1024 + 1, 2 * 256 * 1024 + 5)
+CARRY_TILE_BYTES = 1024      # the device's carry scan walks the output 256 32-bit words at a time
+_long_cache = {}
+
+
+def long_raw_stream(n):
+    """uint16 records of random_stream(n, n), made once"""
+    if n not in _long_cache:
+        rng = np.random.default_rng(1000 + n)        # random_stream's draws, without a Python list of n records
+        p = rng.integers(1, 256, n)
+        bit = rng.random(n) >= p / 256.0
+        _long_cache[n] = ((bit.astype(np.uint16) << 8) | p.astype(np.uint16)).astype(np.uint16)
+    return _long_cache[n]
+
+
+def long_straddle(pad=0):
+    """(uint16 records, byte range [first, end) of its one carry walk) of straddle_stream(40000, 0, pad): 0xff bytes over more than two whole
+    tiles of the carry scan, which only hand the carry on"""
+    key = ("straddle", pad)
+    if key not in _long_cache:
+        st = {}
+        s = np.array(straddle_stream(40000, 0, pad)[0], np.uint16)
+        serial_write(s, st)
+        assert st["carry_events"] == 1
+        _long_cache[key] = (s, st["runs"][0])
+    return _long_cache[key]
+
+
 _raw_cache = None
 
 

@@ -338,3 +338,86 @@ def host_chain(name):
     tile = BM.host_code(tokens=tok["tokens"], bools=m["bools"], segments=segs)[0]
     only = BM.host_code(bools=m["bools"], segments=[s for s in segs if s[2] == 1])[0]
     return tile, only, m
+
+
+# ---------------------------------------------------------------------------------------------------
+# pictures past the first pass of the scans, and at the ceilings of the staging arrays (regenerated from seeds, shared by the CPU and
+# the GPU tests of one process, left unchanged)
+# ---------------------------------------------------------------------------------------------------
+# (name, width, height, kind, seed): 17 x 17 = 289 SBs (odd, more than 256, partial SBs on both edges); the all-4x4 one has more than
+# 256 x 1024 tokens + bools, the bool coder's items
+BIG = (("big_random", 1080, 1080, "random", 43), ("big_4x4", 1080, 1080, 0, 44))
+_big_cache = {}
+
+
+def big_pictures():
+    """[dict(name, W, H, lf_mi, qcoeff, eob_map)] of BIG"""
+    for name, W, H, kind, seed in BIG:
+        if name not in _big_cache:
+            lf, q, emap = make_picture(W, H, kind, seed)
+            _big_cache[name] = dict(name=name, W=W, H=H, lf_mi=lf, qcoeff=q, eob_map=emap)
+    return [_big_cache[b[0]] for b in BIG]
+
+
+def big_host(name):
+    """the host forms on a picture of big_pictures(): dict(tok, modes, segs, tile) -- computed once"""
+    p = next(p for p in big_pictures() if p["name"] == name)
+    if "host" not in p:
+        tok = TM.host_tokenize_picture(p["lf_mi"], p["qcoeff"], p["eob_map"], p["W"], p["H"])
+        m = host_modes(p["lf_mi"], p["eob_map"], tok["tok_off"], p["W"], p["H"])
+        assert m["rc"] == 0 and m["n_bools"] != B.MODES_BAD_GRID
+        seg = m["segments"]
+        segs = list(zip(seg["first"].tolist(), seg["count"].tolist(), seg["kind"].tolist()))
+        p["host"] = dict(tok=tok, modes=m, segs=segs, tile=BM.host_code(tokens=tok["tokens"], bools=m["bools"], segments=segs)[0])
+    return p["host"]
+
+
+DENSE_VALUES = (1, 2, 3, 4, 5, 9, 20, 67, 300)      # every class of energy, CAT6 among them
+_dense_cache = {}
+
+
+def dense_picture(W, H, leaf_type, seed, short=False, ones=False, values=DENSE_VALUES):
+    """(lf_mi, qcoeff, eob_map) of a picture of leaves of one type in which every unit is coded and every coefficient is non-zero (a
+    random value of `values` with a random sign; ones: all 1), eob = n in every transform block: 6144 tokens in every whole SB, and for
+    type 0 its 384 transform blocks.  short: every other transform block has eob = n - 1 and a zero at its last scan position -- still n
+    records, the last one the EOB token.  W, H: multiples of the leaf's size."""
+    key = (W, H, leaf_type, seed, short, ones, tuple(values))
+    if key in _dense_cache:
+        return _dense_cache[key]
+    rng = np.random.default_rng(seed)
+    mi_rows, mi_cols, n_u = H // 8, W // 8, UNITS[leaf_type]
+    assert mi_rows % n_u == 0 and mi_cols % n_u == 0
+    lf = np.zeros((mi_rows, mi_cols), B.LF_MODE_INFO_DTYPE)
+    q = np.zeros(T.n_sb(W, H) * B.SB_COEFFS, np.int16)
+    eoff = eob_offsets(W, H)
+    emap = np.zeros(eoff[3], np.uint16)
+    offs, scans = TM.scan_tables()
+    sb_cols, k = (W + 63) // 64, 0
+    lf["sb_type"], lf["tx_size"], lf["filter_level"] = leaf_type, TX[leaf_type], 12
+    for r in range(0, mi_rows, n_u):
+        for c in range(0, mi_cols, n_u):
+            modes = [int(m) for m in rng.integers(0, 10, 4)]
+            uv = int(rng.integers(0, 10))
+            lf[r:r + n_u, c:c + n_u]["pad"] = (modes[2] | modes[3] << 4, modes[0] | modes[1] << 4, uv) if leaf_type == 0 else (0, modes[0], uv)
+            for plane, x4, y4, ts, i in leaf_tx_blocks(leaf_type, r, c):
+                n, u = 16 << (2 * ts), 8 if plane else 16
+                tt = TM.INTRA_TX_TYPE[modes[i] if leaf_type == 0 else modes[0]] if plane == 0 and ts < 3 else 0
+                scan = scans[offs[(ts, tt)]:offs[(ts, tt)] + n].astype(np.int64)
+                v = np.ones(n, np.int16) if ones else (rng.choice(values, n) * rng.choice((-1, 1), n)).astype(np.int16)
+                eob = n
+                if short and k & 1:
+                    eob, v[n - 1] = n - 1, 0
+                k += 1
+                base = ((y4 // u) * sb_cols + x4 // u) * B.SB_COEFFS + (0, 4096, 5120)[plane] + _zorder(x4 % u, y4 % u) * 16
+                q[base + scan] = v
+                emap[eoff[plane] + y4 * (W // 8 if plane else W // 4) + x4] = eob
+    _dense_cache[key] = (lf, q, emap)
+    return _dense_cache[key]
+
+
+# (width, height, leaf type, seed, keyword arguments) of the dense pictures the tests share.  576x64 = 9 SBs: a full run of 8 SBs in one
+# workgroup of the tokeniser's emit kernel (49 152 tokens) and a second workgroup; 512x64 = that run alone.  `ones` puts all 32 096
+# band-5 luma positions of the run into one bin of the counts (the most a bin can receive: its dword partner, the same row's ZERO
+# token, is then empty); `values=(19, 35)` splits the same positions over the two halves of one dword (tokens 8 and 9, one energy class).
+DENSE = ((576, 64, 0, 51, {}), (576, 64, 0, 52, dict(short=True)), (576, 64, 12, 53, {}), (576, 64, 12, 54, dict(short=True)),
+         (512, 64, 12, 55, dict(ones=True)), (512, 64, 12, 56, dict(values=(19, 35))))

@@ -176,3 +176,26 @@ def test_batch_entry_point_refuses_before_it_touches_a_device():
     assert rc([stream(d_bytes=None)]) != 0 and rc([stream(d_segments=None)]) != 0 and rc([stream(d_segments=None, n_segments=0, n_tokens=4)]) != 0
     assert rc([stream()]) != 0 and b"set_tables" in lib.svt_hip_last_error()      # well-formed, but the context has no tables
     assert not out.any() and not size.any()
+
+
+# ---- past one pass of the device's scans (the host form pinned by the model here; the device is compared with it in test_gpu_boolcode.py)
+@pytest.mark.parametrize("n", BM.LONG_RAW)
+def test_long_raw_streams_host_and_model(n):
+    a = BM.long_raw_stream(n)
+    assert len(a) == n
+    got, size, guard = BM.host_code(bools=a, segments=[(0, n, 1)])
+    assert got == BM.serial_write(a.tolist()) and size == len(got) and np.all(guard == 0xA5)
+
+
+def test_long_straddle_carries_through_whole_tiles():
+    """one carry event whose run of 0xff bytes covers two whole 1024-byte tiles of the device's carry scan"""
+    a, (first, end) = BM.long_straddle()
+    T_ = BM.CARRY_TILE_BYTES
+    j = (first + T_ - 1) // T_
+    assert T_ * (j + 2) <= end, (first, end)
+    st = {}
+    want = BM.serial_write(a.tolist(), st)
+    assert st["carry_events"] == 1 and st["runs"] == [(first, end)]
+    assert not any(want[first:end]) and want[first - 1] != 0           # the walk turned the whole run to zero bytes
+    got, size, guard = BM.host_code(bools=a, segments=[(0, len(a), 1)])
+    assert got == want and size == len(want) and np.all(guard == 0xA5)

@@ -19,4 +19,7 @@ def test_kernel_text_on_the_cpu_equals_the_host_form():
             f.write(BM.tables()[1].tobytes())
         r = subprocess.run([exe, tab], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "bad 0" in r.stdout and "MISMATCH" not in r.stdout, r.stdout + r.stderr
-        assert r.stdout.count(" ok") == 14
+        assert r.stdout.count(" ok") == 16
+        # the last two streams (a segment list over tokens and bools; raw bools alone) take a second pass of the scan over 256 tiles of 1024 items
+        items = [int(line.split(" items ")[1].split()[0]) for line in r.stdout.splitlines() if " items " in line]
+        assert len(items) == 16 and max(items[:14]) < 256 * 1024 < min(items[14:])

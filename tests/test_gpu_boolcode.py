@@ -1,6 +1,7 @@
 """GPU: the bool coder (csrc/boolcode.hip) through the C ABI, byte for byte against the host form (svt_hip_boolcode_host) and the
 reference's bytes (tests/golden/boolcode_reference.npz): chunk and tile boundaries, carries placed on them, contribution pile-up,
-batches with the capacity guard, segment lists, the chain behind encode pass and tokeniser without a host round trip, scratch reuse."""
+batches with the capacity guard, segment lists, the chain behind encode pass and tokeniser without a host round trip, scratch reuse;
+and streams of more than 256 x 1024 items (a second pass of the tile scan) and a carry through whole tiles of the carry scan."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 import boolcode_model as BM
+import modes_model as MM
 import svt_testlib as T
 import tokenize_model as TM
 from test_gpu_encdec import dev, flags_of, make_inputs, md_host
@@ -18,7 +20,7 @@ import gen_golden_tokens as G
 B = T.B
 pytestmark = pytest.mark.gpu
 GUARD = 0x5A
-CARRY_TILE_BYTES = 1024      # svt_bc_carry_kernel walks the accumulator 256 32-bit words at a time
+CARRY_TILE_BYTES = BM.CARRY_TILE_BYTES      # svt_bc_carry_kernel walks the accumulator 256 32-bit words at a time
 
 
 def geometry():
@@ -305,3 +307,32 @@ def test_host_pointer_form(ctx):
     got, size, guard = BM.product_call(B.load().svt_hip_boolcode, bools=a, segments=[(0, len(a), 1)], capacity=20, ctx=ctx)
     want = bytes(BM.fixture()["raw_bytes|straddle_600_1"])
     assert got == want[:20] and size == len(want) and np.all(guard == 0xA5)
+
+
+# ---- past one pass of the scans ------------------------------------------------------------------------------------------------
+def test_long_raw_streams_in_one_batch(ctx):
+    """n bools around 256 tiles of 1024 items, and two passes + 5: the sum the tile scan carries from pass to pass"""
+    check(ctx, [raw(BM.long_raw_stream(n)) for n in BM.LONG_RAW], BM.LONG_RAW)
+
+
+def test_carry_through_whole_tiles_of_the_carry_scan(ctx):
+    """one carry through about 3550 bytes of 0xff: tiles of 256 words that generate nothing and only hand the carry on; then the same stream
+    moved so that the carry starts in the next tile"""
+    a, (first, end) = BM.long_straddle()
+    j = (first + CARRY_TILE_BYTES - 1) // CARRY_TILE_BYTES
+    assert CARRY_TILE_BYTES * (j + 2) <= end
+    tile = end // CARRY_TILE_BYTES
+    pad = 8 * ((tile + 1) * CARRY_TILE_BYTES + 100 - end)
+    b, (first_b, end_b) = BM.long_straddle(pad)
+    assert end_b // CARRY_TILE_BYTES == tile + 1 and end_b - first_b == end - first
+    check(ctx, [raw(a), raw(b)], ("straddle", "padded"))
+
+
+def test_big_picture_tokens_and_segments(ctx):
+    """the all-4x4 1080x1080 picture's tokens, bools and segment list (289 x 256 slots, empty ones among them) from host arrays: 821 785 items"""
+    h = MM.big_host("big_4x4")
+    tok, bools, segs = h["tok"]["tokens"], h["modes"]["bools"], h["segs"]
+    assert len(segs) == 289 * 256 and sum(c for _, c, _ in segs) == len(tok) + len(bools) > 3 * 256 * 1024 and sum(1 for s in segs if s[1] == 0) > 20000
+    s = Stream(tokens=tok, bools=bools, segments=segs)
+    got, size, guard = run(ctx, [s])[0]
+    assert size == len(h["tile"]) and got == h["tile"] and np.all(guard == GUARD)

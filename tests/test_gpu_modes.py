@@ -1,6 +1,7 @@
 """GPU: the key-frame mode-info stage (csrc/modeinfo.hip) through the C ABI, exactly against the host form (svt_hip_modes_kf_picture) and
 the reference's tile bytes (tests/golden/modes_reference.npz): pictures singly and in batches, the chain tokeniser -> mode info -> bool
-coder without a host round trip, the same chain behind the intra encode pass on a searched grid, capacity guard, malformed grids."""
+coder without a host round trip, the same chain behind the intra encode pass on a searched grid, capacity guard, malformed grids; and,
+against the host forms alone (which test_modes.py pins to the serial models), pictures of 289 SBs, the unit with the most bools, wider grids."""
 import ctypes as C
 
 import numpy as np
@@ -14,7 +15,7 @@ import svt_testlib as T
 import tokenize_model as TM
 from test_gpu_encdec import dev, flags_of
 from test_gpu_tokenize import KEY, TokBuffers, tokenize_device, upload
-from test_modes import edge_crossing_grid, malformed_grids
+from test_modes import edge_crossing_grid, malformed_grids, worst_unit_grid
 
 B = T.B
 pytestmark = pytest.mark.gpu
@@ -56,11 +57,11 @@ class ModesBuffers:
                     n_guard=n[1:])
 
 
-def modes_device(ctx, W, H, inputs, bufs=None):
+def modes_device(ctx, W, H, inputs, bufs=None, mi_stride=None):
     """inputs: [(lf_t, emap_t, tok_off_t)] device tensors.  Enqueues one svt_hip_modes_kf_batch_device; returns the buffers (not yet synchronised)"""
     bufs = bufs or [ModesBuffers(W, H) for _ in inputs]
     arr = (B.ModesPicture * len(inputs))(*[b.struct(*i) for b, i in zip(bufs, inputs)])
-    B.check(B.load().svt_hip_modes_kf_batch_device(ctx, len(inputs), arr, W, H, W // 8))
+    B.check(B.load().svt_hip_modes_kf_batch_device(ctx, len(inputs), arr, W, H, mi_stride or W // 8))
     return bufs
 
 
@@ -260,3 +261,85 @@ def test_entry_point_refusals(ctx):
         lib.svt_hip_ctx_destroy(fresh)
     torch.cuda.synchronize()
     assert np.all(b.result()["seg_guard"] == GUARD32) and b.result()["n_bools"] == GUARD32          # nothing ran
+
+
+# ---- past the first pass of the scans, the unit at its ceiling, wider grids ------------------------------------------------------
+def upload_grid(lf_mi, eob_map, tok_off):
+    return dev(np.ascontiguousarray(lf_mi).view(np.uint8)), dev(np.ascontiguousarray(eob_map).view(np.int16)), dev(np.ascontiguousarray(tok_off).view(np.int32))
+
+
+def test_big_pictures_in_one_batch_full_and_half_capacity(ctx):
+    """289 SBs: two entries a lane in the SB scan, an odd SB count under the batch's % and /, 73 workgroups of the emit kernel a picture, the
+    last with one live wave"""
+    pics = MM.big_pictures()
+    W, H = pics[0]["W"], pics[0]["H"]
+    assert T.n_sb(W, H) == 289
+    host = [MM.big_host(p["name"]) for p in pics]
+    inputs = [upload_grid(p["lf_mi"], p["eob_map"], h["tok"]["tok_off"]) for p, h in zip(pics, host)]
+    torch.cuda.synchronize()
+    bufs = modes_device(ctx, W, H, inputs)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    for b, h in zip(bufs, host):
+        same(b.result(), h["modes"])
+    half = host[1]["modes"]["n_bools"] // 2
+    bufs = [ModesBuffers(W, H), ModesBuffers(W, H, capacity=half)]
+    modes_device(ctx, W, H, inputs, bufs)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    same(bufs[0].result(), host[0]["modes"])
+    got, want = bufs[1].result(), host[1]["modes"]
+    assert got["n_bools"] == want["n_bools"] and np.array_equal(got["bools"], want["bools"][:half]) and np.array_equal(got["segments"], want["segments"])
+    assert np.all(got["guard"] == GUARD16) and len(got["guard"]) == 64 and np.all(got["seg_guard"] == GUARD32) and np.all(got["n_guard"] == GUARD32)
+
+
+def test_worst_unit_on_the_device(ctx):
+    """the unit that reaches SVT_MI_UNIT_BOOLS: the wave's part of LDS is sized by it"""
+    lf = worst_unit_grid()
+    lf["skip"] = 1
+    W = H = 64
+    emap = np.zeros(MM.eob_offsets(W, H)[3], np.uint16)
+    tok_off = np.full(emap.size, 0xFFFFFFFF, np.uint32)
+    want = MM.host_modes(lf, emap, tok_off, W, H)
+    assert want["rc"] == 0 and want["segments"]["count"][want["segments"]["kind"] == 1].max() == B.MODES_UNIT_BOOLS
+    inputs = [upload_grid(lf, emap, tok_off)]
+    torch.cuda.synchronize()
+    bufs = modes_device(ctx, W, H, inputs)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    same(bufs[0].result(), want)
+
+
+def test_device_chain_on_the_big_4x4_picture(ctx):
+    """tokeniser -> mode info -> bool coder on 294 054 tokens + 527 731 bools: four passes of the bool coder's tile scan, 324 tiles of its carry scan"""
+    p, h = MM.big_pictures()[1], MM.big_host("big_4x4")
+    assert p["name"] == "big_4x4" and len(h["tok"]["tokens"]) + h["modes"]["n_bools"] > 3 * 256 * 1024 and len(h["tile"]) > 256 * 1024
+    W, H = p["W"], p["H"]
+    lf_t, q_t, emap_t = upload(p["lf_mi"], p["qcoeff"], p["eob_map"])
+    tb, mb, tile = chain(ctx, W, H, lf_t, q_t, emap_t)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    same(mb.result(), h["modes"])
+    got_tok = tb.result()
+    assert np.array_equal(got_tok["tokens"], h["tok"]["tokens"]) and np.array_equal(got_tok["tok_off"], h["tok"]["tok_off"]) and np.all(got_tok["guard"] == GUARD32)
+    got, size, guard = tile.result()
+    assert size == len(h["tile"]) and got == h["tile"] and np.all(guard == GUARD8)
+
+
+@pytest.mark.parametrize("name", ("edge_72x40_a", "sbs_136x136_a", "big_random"))
+def test_wider_grid_equals_the_tight_host_form(ctx, name):
+    """mi_stride = mi_cols + 9 with random bytes behind every row of the grid, through the tokeniser and the mode-info stage"""
+    if name.startswith("big"):
+        p, h = next(p for p in MM.big_pictures() if p["name"] == name), MM.big_host(name)
+        tok, want = h["tok"], h["modes"]
+    else:
+        p, tok = MM.fixture_picture(name), MM.host_tokens(name)
+        want = host_of(name)
+    W, H = p["W"], p["H"]
+    wide = TM.with_stride(p["lf_mi"], 9, 4)
+    lf_t, q_t, emap_t = upload(wide, p["qcoeff"], p["eob_map"])
+    tb, mb = TokBuffers(W, H, counts=False), ModesBuffers(W, H)
+    torch.cuda.synchronize()
+    tokenize_device(ctx, W, H, [(lf_t, q_t, emap_t)], [tb], mi_stride=W // 8 + 9)
+    modes_device(ctx, W, H, [(lf_t, emap_t, tb.tok_off)], [mb], mi_stride=W // 8 + 9)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    got_tok = tb.result()
+    for out in ("tokens", "tok_off", "sb_off"):
+        assert np.array_equal(got_tok[out], tok[out]), out
+    same(mb.result(), want)

@@ -1,6 +1,7 @@
 """GPU: the coefficient tokeniser (csrc/tokenize.hip) through the C ABI -- block form against the numpy model and the reference's rate by
 the cost identity, picture form against the reference's eb_vp9_tokenize_sb (tests/golden/tokens_reference.npz), batches, capacity
-guard, the chain behind the encode pass without a host round trip, and scratch reuse across picture sizes."""
+guard, the chain behind the encode pass without a host round trip, scratch reuse across picture sizes; and, against the host form alone
+(which test_tokenize.py pins to the model), pictures of 289 SBs, SBs whose every block slot and token is used, wider grids."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 import encdec_model as M
+import modes_model as MM
 import svt_testlib as T
 import tokenize_model as TM
 from test_gpu_encdec import DevPicture, _chroma, dev, flags_of, make_inputs, md_host
@@ -314,3 +316,70 @@ def synthetic_picture(rng, lf, W, H):
             r0, c0 = r - r % n8, c - c % n8
             lf["skip"][r, c] = 0 if coded[r0:r0 + n8, c0:c0 + n8].any() else 1
     return lf, q, emap
+
+
+# ---- 10. past the first pass of the scans, full staging arrays, wider grids ------------------------------------------------------
+def run_pictures(ctx, W, H, pics, bufs=None, mi_stride=None):
+    """pics: [(lf_mi, qcoeff, eob_map)] host arrays through one batch call -> the results"""
+    inputs = [upload(*p) for p in pics]
+    torch.cuda.synchronize()
+    bufs = tokenize_device(ctx, W, H, inputs, bufs, mi_stride)
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    return [b.result() for b in bufs]
+
+
+def test_big_pictures_in_one_batch(ctx):
+    """289 SBs: two entries a lane in the SB scan (and lanes with none), 37 workgroups of the emit kernel a picture, the last with one SB"""
+    pics = MM.big_pictures()
+    assert len({(p["W"], p["H"]) for p in pics}) == 1 and T.n_sb(pics[0]["W"], pics[0]["H"]) == 289
+    got = run_pictures(ctx, pics[0]["W"], pics[0]["H"], [(p["lf_mi"], p["qcoeff"], p["eob_map"]) for p in pics])
+    for p, g in zip(pics, got):
+        same(g, MM.big_host(p["name"])["tok"])
+
+
+@pytest.mark.parametrize("size", sorted({d[:2] for d in MM.DENSE}))
+def test_dense_pictures_equal_the_host_form(ctx, size):
+    """every SB at 6144 tokens (49 152 in a workgroup's run), 384 block slots for units of 4x4 blocks, one bin of the counts at 32 096"""
+    W, H = size
+    cases = [d for d in MM.DENSE if d[:2] == size]
+    pics = [MM.dense_picture(w, h, t, seed, **kw) for w, h, t, seed, kw in cases]
+    host = [TM.host_tokenize_picture(*p, W, H) for p in pics]
+    for g, h in zip(run_pictures(ctx, W, H, pics), host):
+        assert np.all(np.diff(h["sb_off"].astype(np.int64)) == 6144)
+        same(g, h)
+    if size == (512, 64):
+        assert max(int(h["counts"].max()) for h in host) == 32096
+
+
+def test_dense_picture_one_record_short(ctx):
+    W, H, t, seed, kw = MM.DENSE[0]
+    assert t == 0
+    pic = MM.dense_picture(W, H, t, seed, **kw)
+    full = TM.host_tokenize_picture(*pic, W, H)
+    total = int(full["sb_off"][-1])
+    assert total == 6144 * 9
+    got = run_pictures(ctx, W, H, [pic], [TokBuffers(W, H, capacity=total - 1)])[0]
+    assert int(got["sb_off"][-1]) == total and np.all(got["guard"] == GUARD) and len(got["guard"]) == 64
+    assert np.array_equal(got["tokens"], full["tokens"][:-1])
+    for name in ("tok_off", "sb_off", "counts"):
+        assert np.array_equal(got[name], full[name]), name
+
+
+def test_block_form_above_1024_blocks(ctx):
+    """more than 2048 blocks: three entries a lane in the block scan"""
+    case = T.make_rate_case(3, 512, 256)
+    assert len(case["blocks"]) > 2048
+    m_tok, m_off, m_cnt = TM.tokenize_blocks(case)
+    tok, off, cnt, guard = device_blocks(ctx, case)
+    assert np.array_equal(off, m_off) and np.array_equal(tok, m_tok) and np.array_equal(cnt, m_cnt) and np.all(guard == 0xA5A5A5A5)
+
+
+@pytest.mark.parametrize("name", ("edge_72x40_a", "sbs_136x136_a", "big_random"))
+def test_picture_form_on_a_wider_grid(ctx, name):
+    """mi_stride = mi_cols + 9 with random bytes behind every row of the grid: the tight grid's host results"""
+    p = MM.fixture_picture(name) if name in MM.NAMES else next(p for p in MM.big_pictures() if p["name"] == name)
+    W, H = p["W"], p["H"]
+    tight = MM.big_host(name)["tok"] if name.startswith("big") else TM.host_tokenize_picture(p["lf_mi"], p["qcoeff"], p["eob_map"], W, H)
+    wide = TM.with_stride(p["lf_mi"], 9, 3)
+    assert wide.shape == (H // 8, W // 8 + 9)
+    same(run_pictures(ctx, W, H, [(wide, p["qcoeff"], p["eob_map"])], mi_stride=W // 8 + 9)[0], tight)

@@ -9,6 +9,7 @@ import pytest
 import boolcode_model as BM
 import modes_model as MM
 import svt_testlib as T
+import tokenize_model as TM
 
 B = T.B
 NAMES = MM.NAMES
@@ -204,3 +205,40 @@ def test_bad_arguments():
     arr = (B.ModesPicture * 1)(B.ModesPicture())
     assert lib.svt_hip_modes_kf_batch_device(fake_ctx, 1, arr, 64, 64, 8) != 0 and lib.svt_hip_modes_kf_batch_device(fake_ctx, 33, arr, 64, 64, 8) != 0
     assert lib.svt_hip_modes_kf_batch_device(None, 1, arr, 64, 64, 8) != 0 and lib.svt_hip_modes_set_tables(None, None) != 0
+
+
+# ---- past the first pass of the scans, and on wider grids (the host forms pinned by the serial models here; the device is compared with
+# the host forms in test_gpu_modes.py) ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [b[0] for b in MM.BIG])
+def test_big_picture_host_chain_equals_the_serial_models(name):
+    """289 SBs (more than the 256 lanes of the SB scans, odd, partial on both edges); the all-4x4 picture has more tokens + bools than
+    one pass of the bool coder's scan over 256 tiles of 1024 items takes"""
+    p, h = next(p for p in MM.big_pictures() if p["name"] == name), MM.big_host(name)
+    W, H, tok, m = p["W"], p["H"], h["tok"], h["modes"]
+    assert T.n_sb(W, H) == 289 and len(m["segments"]) == 289 * 256
+    if name == "big_4x4":
+        assert len(tok["tokens"]) + m["n_bools"] > 256 * 1024
+    recs, leaves = MM.serial_walk(p["lf_mi"], W, H, MM.tables()[0])
+    assert m["n_bools"] == len(recs) <= B.load().svt_hip_modes_bools_capacity(W, H) and np.array_equal(m["bools"], recs)
+    assert np.all(m["guard"] == 0xA5A5) and np.all(m["seg_guard"] == 0x5A5A5A5A)
+    runs = MM.leaf_runs(p["lf_mi"], tok["tok_off"], p["eob_map"], W, H)
+    order = MM.coding_order_segments(leaves, runs)
+    assert [s for s in h["segs"] if s[1]] == order
+    assert BM.serial_write(BM.expand(tok["tokens"], recs, order, BM.tables()[0])) == h["tile"]
+
+
+@pytest.mark.parametrize("name", ("edge_72x40_a", "sbs_136x136_a", "big_random"))
+def test_host_form_on_a_wider_grid(name):
+    """mi_stride = mi_cols + 9, random bytes in the records behind the picture: every output as on the tight grid"""
+    if name.startswith("big"):
+        p, h = next(p for p in MM.big_pictures() if p["name"] == name), MM.big_host(name)
+        tok, tight = h["tok"], h["modes"]
+    else:
+        p, tok = MM.fixture_picture(name), MM.host_tokens(name)
+        tight = MM.host_modes(p["lf_mi"], p["eob_map"], tok["tok_off"], p["W"], p["H"])
+    wide = TM.with_stride(p["lf_mi"], 9, 2)
+    assert wide.shape[1] == p["W"] // 8 + 9 and wide[:, p["W"] // 8:]["sb_type"].max() > 12
+    got = MM.host_modes(wide, p["eob_map"], tok["tok_off"], p["W"], p["H"])
+    assert got["rc"] == tight["rc"] == 0 and got["n_bools"] == tight["n_bools"] != B.MODES_BAD_GRID
+    assert np.array_equal(got["bools"], tight["bools"]) and np.array_equal(got["segments"], tight["segments"])
+    assert np.all(got["guard"] == 0xA5A5) and np.all(got["seg_guard"] == 0x5A5A5A5A)

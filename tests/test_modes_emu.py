@@ -1,6 +1,6 @@
 """CPU: the mode-info stage's kernels themselves (csrc/modeinfo.hip compiled as plain C++ against tests/emu/modeinfo/hip/hip_runtime.h,
 one thread per lane) against svt_hip_modes_kf_picture on the fixture pictures, singly and as batches of one geometry, with full, short and
-no bool capacity, and on the malformed grids -- the count, the scan, the LDS assembly, the dword stores and the segment slots as the
+no bool capacity, on the malformed grids, on the unit with the most bools and on 1080x1080 pictures of 289 SBs -- the count, the scan, the LDS assembly, the dword stores and the segment slots as the
 device runs them, without a device."""
 import os
 import struct
@@ -11,7 +11,7 @@ import numpy as np
 
 import modes_model as MM
 import svt_testlib as T
-from test_modes import edge_crossing_grid, malformed_grids
+from test_modes import edge_crossing_grid, malformed_grids, worst_unit_grid
 
 B = T.B
 
@@ -33,6 +33,18 @@ def test_kernel_text_on_the_cpu_equals_the_host_form():
         emap = np.zeros(MM.eob_offsets(W, H)[3], np.uint16)
         good = "sb64_leaf3" if W == 64 else "edge_72x40_a"
         groups.append(((W, H), [(int(lib.svt_hip_modes_bools_capacity(W, H)), lf, emap, np.full(emap.size, 0xFFFFFFFF, np.uint32)) for lf in grids] + [fixture_case(good)]))
+    # the unit that reaches SVT_MI_UNIT_BOOLS (every unit of the SB at its ceiling but for the partition symbols), beside a fixture picture
+    worst = worst_unit_grid()
+    worst["skip"] = 1
+    emap = np.zeros(MM.eob_offsets(64, 64)[3], np.uint16)
+    groups.append(((64, 64), [(int(lib.svt_hip_modes_bools_capacity(64, 64)), worst, emap, np.full(emap.size, 0xFFFFFFFF, np.uint32)), fixture_case("sb64_leaf0")]))
+    # 289 SBs: two entries per lane of the SB scan and lanes with none, an odd SB count under the batch's % and /, a last workgroup of the
+    # emit kernel with one live wave; with room for every bool and for half of them
+    big = []
+    for p in MM.big_pictures():
+        h = MM.big_host(p["name"])
+        big += [(cap, p["lf_mi"], p["eob_map"], h["tok"]["tok_off"]) for cap in (int(lib.svt_hip_modes_bools_capacity(p["W"], p["H"])), h["modes"]["n_bools"] // 2)]
+    groups.append(((1080, 1080), big))
     n_pics = sum(len(g[1]) for g in groups)
     emu, src = os.path.join(T.ROOT, "tests", "emu", "modeinfo"), os.path.join(T.ROOT, "svt-vp9_amd")
     with tempfile.TemporaryDirectory() as td:

@@ -287,6 +287,16 @@ def host_tokenize_picture(lf_mi, qcoeff, eob_map, W, H, capacity=None, counts=Tr
     return dict(tokens=tokens[:min(int(sb_off[-1]), cap)].copy(), tok_off=tok_off, sb_off=sb_off, counts=cnt if counts else None, guard=tokens[cap:])
 
 
+def with_stride(lf_mi, extra, seed=0):
+    """the grid in rows `extra` records wider (mi_stride = mi_cols + extra; the wrappers above take the stride from the array's shape):
+    the records behind the picture's last column hold random bytes, which nothing may read"""
+    rows, cols = lf_mi.shape
+    noise = np.random.default_rng(7000 + seed).integers(0, 256, rows * (cols + extra) * lf_mi.dtype.itemsize, dtype=np.uint8)
+    wide = noise.view(lf_mi.dtype).reshape(rows, cols + extra).copy()
+    wide[:, :cols] = lf_mi
+    return wide
+
+
 # ---------------------------------------------------------------------------------------------------
 # blocks at the boundaries of the token classes (shared by the CPU and the GPU tests)
 # ---------------------------------------------------------------------------------------------------
