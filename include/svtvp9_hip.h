@@ -739,7 +739,8 @@ int32_t svt_hip_coeff_rate_batch(svt_hip_ctx *ctx, const int16_t *qcoeff, size_t
  * Replaces eb_vp9_tokenize_sb -> tokenize_b (VPX/vp9_tokenize.c:275-349, 397-430) as eb_vp9_entropy_coding_kernel calls it for
  * every coded block in front of the bool coder (Codec/EbEntropyCodingProcess.c:381-398).  The reference codes with the default
  * probabilities (its count-based update is compiled out, VPX/vp9_tokenize.c:301-304), so a token stream plus the fixed tables is
- * all the arithmetic coder needs; the coder itself, the headers and the packets stay on the host.
+ * all the arithmetic coder needs (the bool coder and the mode-info stages of key frames and of inter pictures follow below); the
+ * headers and the packets stay on the host.
  *
  * One token = one uint32_t record: extra << 16 | prob_row << 4 | token.
  *   token     ZERO 0, ONE..FOUR 1..4, CAT1..CAT6 5..10 (|v| 5-6, 7-10, 11-18, 19-34, 35-66, >= 67), EOB 11 (at scan position eob
@@ -823,8 +824,9 @@ uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
  *   segment       {first, count, kind}: kind 0 = `count` token records from d_tokens + first, kind 1 = `count` bool records from
  *                 d_bools + first.  Segments are coded in list order; a transform block never straddles two segments.
  * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
- * uploaded once per context.  The raw bools and the segment list of a key frame's tile come from the mode-info stage below; inter
- * pictures' mode info, the uncompressed and compressed headers and packet delivery are not on the device. */
+ * uploaded once per context.  The raw bools and the segment list of a tile come from the mode-info stages below (key frames:
+ * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device); the derivation of the MV references, the
+ * uncompressed and compressed headers and packet delivery are not on the device. */
 typedef struct svt_bool_tables {
     uint8_t coef_probs[576 * 3]; /* [prob_row][node]: cm->fc->coef_probs flattened */
     uint8_t pareto[255][8];      /* eb_vp9_pareto8_full */
@@ -926,6 +928,85 @@ int32_t svt_hip_modes_kf_picture(const svt_modes_tables *tables, const svt_modes
  * 48 = 4 partition symbols of 3 bools + skip + (4 luma modes + the chroma mode) of 7 bools */
 uint32_t svt_hip_modes_segments(int32_t width, int32_t height);
 uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Inter mode-info syntax: the grid of an inter picture -> the raw bools and the segment list of its tile, the counterpart of the
+ * key-frame entry above for every other picture.
+ *
+ * Replaces what eb_vp9_entropy_coding_kernel codes per block in front of its tokens in a picture that is not intra-only
+ * (Codec/EbEntropyCodingProcess.c:60-449): write_partition (VPX/vp9_bitstream.c:399-417) under the frame's partition probabilities
+ * and pack_inter_mode_mvs (:206-321) at every leaf -- skip, intra/inter, then for an intra block its luma mode(s) and chroma mode, for
+ * an inter block the reference frames (write_ref_frames, :170-204), the inter mode and, for NEWMV, one motion-vector difference per
+ * reference (eb_vp9_encode_mv, VPX/vp9_encodemv.c:33-66, 201-220).  No transform size (tx_mode is ALLOW_32X32), no segment id, no
+ * interpolation filter (fixed); no inter block below 8x8.  Every context reads the leaves above and left of the leaf's origin
+ * (VPX/vp9_pred_common.c) and is taken from the grid (csrc/modeinfo_inter_core.h).  Chain: encode pass -> tokeniser -> this -> bool
+ * coder on one context's stream, no host round trip.  mbmi_ext's values -- the MV references and the mode context that
+ * eb_vp9_find_mv_refs derives -- are inputs here exactly as they are inputs of pack_inter_mode_mvs; deriving them, the two headers
+ * and packet delivery are not on the device.
+ *
+ * The tables are the caller's data (the frame context cm->fc), uploaded once per context. */
+typedef struct svt_modes_mv_comp {       /* nmv_component (VPX/vp9_entropymv.h) */
+    uint8_t sign, classes[10], class0[1], bits[10], class0_fp[2][3], fp[3], class0_hp, hp;
+} svt_modes_mv_comp;                     /* 33 bytes */
+typedef struct svt_modes_inter_tables {
+    uint8_t partition_prob[16][3];       /* [4 * level (8x8 .. 64x64) + 2 * left + above][node], as kf_partition_probs */
+    uint8_t skip_probs[3];               /* [above skip + left skip] */
+    uint8_t intra_inter_prob[4];
+    uint8_t comp_inter_prob[5];
+    uint8_t single_ref_prob[5][2];
+    uint8_t comp_ref_prob[5];
+    uint8_t y_mode_prob[4][9];           /* [size group: 4x4 blocks, 8x8, 16x16, 32x32 and 64x64][node] */
+    uint8_t uv_mode_prob[10][9];         /* [luma mode][node] */
+    uint8_t inter_mode_probs[7][3];      /* [mode context][node] */
+    uint8_t mv_joints[3];
+    svt_modes_mv_comp mv_comps[2];       /* 0: vertical (row), 1: horizontal (column) */
+} svt_modes_inter_tables;                /* 291 bytes */
+/* what the grid records lack, one record per 8x8 unit (the grid's mi_stride).  ref_frame is read from every unit (neighbours read
+ * it), the other fields at the origin of a leaf only. */
+typedef struct svt_mi_inter_ext {
+    int16_t ref_mv_row[2], ref_mv_col[2]; /* mbmi_ext->ref_mvs[ref_frame[ref]][0] of ref 0 / ref 1, 1/8 sample */
+    uint8_t ref_frame[2];                 /* 0 intra, 1 LAST, 2 GOLDEN, 3 ALTREF; ref_frame[1] == 0: no second reference */
+    uint8_t mode;                         /* inter block: 10 NEARESTMV, 11 NEARMV, 12 ZEROMV, 13 NEWMV */
+    uint8_t mode_context;                 /* mbmi_ext->mode_context[ref_frame[0]], 0 .. 6 */
+} svt_mi_inter_ext;                       /* 12 bytes */
+#define SVT_MODES_SINGLE_REFERENCE 0
+#define SVT_MODES_COMPOUND_REFERENCE 1
+#define SVT_MODES_REFERENCE_SELECT 2
+/* one picture of a batch; the first eight fields are svt_modes_picture's and mean the same (an intra block keeps its modes in pad_[1],
+ * pad_[2] and the nibbles of pad_[0]).
+ *   d_mc_mi     the grid the encode pass holds: the motion vectors are read from it (mv_row / mv_col of ref 0 / 1)
+ *   d_ext       the extension records
+ *   reference_mode .. ref_frame_sign_bias   cm->reference_mode, cm->allow_high_precision_mv, and what
+ *               eb_vp9_setup_compound_reference_mode leaves in cm->comp_fixed_ref / comp_var_ref from cm->ref_frame_sign_bias
+ *   d_n_bools   SVT_MODES_BAD_GRID also for: an inter block below 8x8; is_inter, d_mc_mi's ref_list and ref_frame disagreeing about
+ *               inter or compound; a reference frame above 3; a compound block under SINGLE_REFERENCE (a single one under
+ *               COMPOUND_REFERENCE) or one whose references are not comp_fixed_ref plus one of comp_var_ref; an inter mode outside
+ *               10 .. 13; mode_context above 6; a motion-vector difference of a NEWMV block beyond +-16383 in a component */
+typedef struct svt_modes_inter_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const uint16_t         *d_eob_map;
+    const uint32_t         *d_tok_off;
+    uint16_t               *d_bools;
+    svt_bool_segment       *d_segments;
+    uint32_t               *d_n_bools;
+    uint32_t                capacity;   /* records d_bools can hold */
+    uint32_t                pad_;
+    const svt_mc_mode_info *d_mc_mi;
+    const svt_mi_inter_ext *d_ext;
+    uint8_t                 reference_mode, allow_hp, comp_fixed_ref, comp_var_ref[2], ref_frame_sign_bias[4];
+    uint8_t                 pad2_[7];
+} svt_modes_inter_picture;              /* 88 bytes */
+int32_t svt_hip_modes_inter_set_tables(svt_hip_ctx *ctx, const svt_modes_inter_tables *tables);
+/* n_pics (<= 32) pictures of one geometry in one call; their frame parameters may differ.  Asynchronous on the context's stream:
+ * behind svt_hip_tokenize_batch_device and in front of svt_hip_boolcode_batch_device it needs no host round trip.  The segment list
+ * has the key-frame entry's format and length (svt_hip_modes_segments). */
+int32_t svt_hip_modes_inter_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_modes_inter_picture *pics, int32_t width, int32_t height,
+                                         int32_t mi_stride);
+/* host form of the same text (csrc/modeinfo_inter_core.h), pure CPU, host pointers; also checks the per-unit bound of the capacity */
+int32_t svt_hip_modes_inter_picture(const svt_modes_inter_tables *tables, const svt_modes_inter_picture *pic, int32_t width, int32_t height,
+                                    int32_t mi_stride);
+/* bools a picture emits at most: its 8x8 units times 111 (derived in csrc/modeinfo_inter_core.h) */
+uint32_t svt_hip_modes_inter_bools_capacity(int32_t width, int32_t height);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.

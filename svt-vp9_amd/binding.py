@@ -181,6 +181,27 @@ class ModesPicture(C.Structure):
     _fields_ = [("d_lf_mi", C.c_void_p), ("d_eob_map", C.c_void_p), ("d_tok_off", C.c_void_p), ("d_bools", C.c_void_p), ("d_segments", C.c_void_p),
                 ("d_n_bools", C.c_void_p), ("capacity", C.c_uint32), ("pad_", C.c_uint32)]
 
+
+# inter mode-info stage (svt_modes_inter_tables / svt_mi_inter_ext / svt_modes_inter_picture of include/svtvp9_hip.h)
+MODES_MV_COMP_DTYPE = np.dtype([("sign", "u1"), ("classes", "u1", (10,)), ("class0", "u1", (1,)), ("bits", "u1", (10,)), ("class0_fp", "u1", (2, 3)), ("fp", "u1", (3,)),
+                                ("class0_hp", "u1"), ("hp", "u1")])
+MODES_INTER_TABLES_DTYPE = np.dtype([("partition_prob", "u1", (16, 3)), ("skip_probs", "u1", (3,)), ("intra_inter_prob", "u1", (4,)), ("comp_inter_prob", "u1", (5,)),
+                                     ("single_ref_prob", "u1", (5, 2)), ("comp_ref_prob", "u1", (5,)), ("y_mode_prob", "u1", (4, 9)), ("uv_mode_prob", "u1", (10, 9)),
+                                     ("inter_mode_probs", "u1", (7, 3)), ("mv_joints", "u1", (3,)), ("mv_comps", MODES_MV_COMP_DTYPE, (2,))])
+assert MODES_MV_COMP_DTYPE.itemsize == 33 and MODES_INTER_TABLES_DTYPE.itemsize == 291
+MI_INTER_EXT_DTYPE = np.dtype([("ref_mv_row", "<i2", (2,)), ("ref_mv_col", "<i2", (2,)), ("ref_frame", "u1", (2,)), ("mode", "u1"), ("mode_context", "u1")])
+assert MI_INTER_EXT_DTYPE.itemsize == 12
+MODES_INTER_UNIT_BOOLS = 111
+MODES_SINGLE_REFERENCE, MODES_COMPOUND_REFERENCE, MODES_REFERENCE_SELECT = 0, 1, 2
+
+
+class ModesInterPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_eob_map", C.c_void_p), ("d_tok_off", C.c_void_p), ("d_bools", C.c_void_p), ("d_segments", C.c_void_p),
+                ("d_n_bools", C.c_void_p), ("capacity", C.c_uint32), ("pad_", C.c_uint32), ("d_mc_mi", C.c_void_p), ("d_ext", C.c_void_p),
+                ("reference_mode", C.c_uint8), ("allow_hp", C.c_uint8), ("comp_fixed_ref", C.c_uint8), ("comp_var_ref", C.c_uint8 * 2),
+                ("ref_frame_sign_bias", C.c_uint8 * 4), ("pad2_", C.c_uint8 * 7)]
+
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -214,6 +235,7 @@ EXPORTS = [
     "svt_hip_boolcode_set_tables", "svt_hip_boolcode_batch_device", "svt_hip_boolcode", "svt_hip_boolcode_host", "svt_hip_boolcode_capacity", "svt_hip_boolcode_bools_capacity",
     "svt_hip_boolcode_geometry",
     "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
+    "svt_hip_modes_inter_set_tables", "svt_hip_modes_inter_batch_device", "svt_hip_modes_inter_picture", "svt_hip_modes_inter_bools_capacity",
 ]
 
 _lib = None
@@ -251,6 +273,7 @@ def load():
         _lib.svt_hip_boolcode_geometry.restype = None
         _lib.svt_hip_modes_segments.restype = C.c_uint32
         _lib.svt_hip_modes_bools_capacity.restype = C.c_uint32
+        _lib.svt_hip_modes_inter_bools_capacity.restype = C.c_uint32
         _u32 = C.c_uint32
         _lib.svt_hip_boolcode_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.POINTER(_u32)]
         _lib.svt_hip_boolcode.argtypes = [C.c_void_p] + _lib.svt_hip_boolcode_host.argtypes[1:]

@@ -1,0 +1,60 @@
+/*
+ * modeinfo_inter_host.c -- host-side (plain C) companions of the inter mode-info stage (csrc/modeinfo_inter.hip):
+ *   - svt_hip_modes_inter_picture, the host form (the same inline text the kernels call, csrc/modeinfo_inter_core.h), which is what the
+ *     CPU tests pin against the reference's write_partition / pack_inter_mode_mvs (VPX/vp9_bitstream.c:206-321, 399-417);
+ *   - the capacity of the bool buffer, a host value.  The segment list has the key-frame stage's length (svt_hip_modes_segments).
+ */
+#include <string.h>
+#include "../../include/svtvp9_hip.h"
+#include "../csrc/modeinfo_inter_core.h"
+
+static int bad_geometry(int32_t width, int32_t height) { return width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7); }
+
+static int bad_frame(const svt_modes_inter_picture *p) {
+    const svt_mii_frame f = svt_mii_frame_of(p);
+    return svt_mii_bad_frame(&f);
+}
+
+uint32_t svt_hip_modes_inter_bools_capacity(int32_t width, int32_t height) {
+    if (bad_geometry(width, height)) return 0;
+    return (uint32_t)((width >> 3) * (height >> 3)) * SVT_MII_UNIT_BOOLS;
+}
+
+int32_t svt_hip_modes_inter_picture(const svt_modes_inter_tables *tables, const svt_modes_inter_picture *pic, int32_t width, int32_t height, int32_t mi_stride) {
+    if (!tables || !pic || !pic->d_lf_mi || !pic->d_mc_mi || !pic->d_ext || !pic->d_eob_map || !pic->d_tok_off || !pic->d_segments || !pic->d_n_bools ||
+        (!pic->d_bools && pic->capacity) || bad_geometry(width, height) || mi_stride < (width >> 3) || bad_frame(pic))
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    const svt_tok_geom g = {mi_stride, height >> 3, width >> 3, width >> 2, height >> 2};
+    const int          sb_cols = (width + 63) >> 6, n_sb = sb_cols * ((height + 63) >> 6);
+    const svt_mii_view v = {pic->d_lf_mi, pic->d_mc_mi, pic->d_ext, svt_mii_frame_of(pic)};
+    memset(pic->d_segments, 0, sizeof(svt_bool_segment) * 256 * (size_t)n_sb);
+    for (int r = 0; r < g.mi_rows; r++)
+        for (int c = 0; c < g.mi_cols; c++)
+            if (svt_mii_check(&v, &g, r, c)) {
+                *pic->d_n_bools = SVT_MODES_BAD_GRID;
+                return SVT_HIP_OK;
+            }
+    uint64_t pos = 0;
+    for (int sb = 0; sb < n_sb; sb++)
+        for (int z = 0; z < 64; z++) {
+            int ur, uc;
+            svt_tok_unit_of(z, &ur, &uc);
+            const int r = (sb / sb_cols) * 8 + ur, c = (sb % sb_cols) * 8 + uc;
+            if (r >= g.mi_rows || c >= g.mi_cols) continue;
+            uint16_t  rec[SVT_MII_UNIT_BOOLS + 64];
+            const int n = svt_mii_unit_bools(&v, &g, r, c, tables, rec);
+            if (n > SVT_MII_UNIT_BOOLS || n != svt_mii_unit_bools(&v, &g, r, c, NULL, NULL)) return SVT_HIP_ERR_BAD_PARAMETER; /* (the bound the capacity rests on) */
+            if (!n) continue;
+            svt_bool_segment *s = pic->d_segments + 4 * ((size_t)sb * 64 + z);
+            uint32_t          first[3], count[3];
+            svt_mi_leaf_tokens(pic->d_lf_mi, pic->d_eob_map, pic->d_tok_off, &g, r, c, first, count);
+            s[0].first = (uint32_t)pos; s[0].count = (uint32_t)n; s[0].kind = 1;
+            for (int p = 0; p < 3; p++)
+                if (count[p]) { s[1 + p].first = first[p]; s[1 + p].count = count[p]; }
+            for (int i = 0; i < n; i++)
+                if (pos + i < pic->capacity) pic->d_bools[pos + i] = rec[i];
+            pos += n;
+        }
+    *pic->d_n_bools = (uint32_t)pos;
+    return SVT_HIP_OK;
+}
