@@ -825,7 +825,7 @@ uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
  *                 d_bools + first.  Segments are coded in list order; a transform block never straddles two segments.
  * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
  * uploaded once per context.  The raw bools and the segment list of a tile come from the mode-info stages below (key frames:
- * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device); the derivation of the MV references, the
+ * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device behind svt_hip_mvrefs_batch_device); the
  * uncompressed and compressed headers and packet delivery are not on the device. */
 typedef struct svt_bool_tables {
     uint8_t coef_probs[576 * 3]; /* [prob_row][node]: cm->fc->coef_probs flattened */
@@ -941,8 +941,8 @@ uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height);
  * interpolation filter (fixed); no inter block below 8x8.  Every context reads the leaves above and left of the leaf's origin
  * (VPX/vp9_pred_common.c) and is taken from the grid (csrc/modeinfo_inter_core.h).  Chain: encode pass -> tokeniser -> this -> bool
  * coder on one context's stream, no host round trip.  mbmi_ext's values -- the MV references and the mode context that
- * eb_vp9_find_mv_refs derives -- are inputs here exactly as they are inputs of pack_inter_mode_mvs; deriving them, the two headers
- * and packet delivery are not on the device.
+ * eb_vp9_find_mv_refs derives -- are inputs here exactly as they are inputs of pack_inter_mode_mvs; svt_hip_mvrefs_batch_device below
+ * derives them on the device.  The two headers and packet delivery are not on the device.
  *
  * The tables are the caller's data (the frame context cm->fc), uploaded once per context. */
 typedef struct svt_modes_mv_comp {       /* nmv_component (VPX/vp9_entropymv.h) */
@@ -1007,6 +1007,60 @@ int32_t svt_hip_modes_inter_picture(const svt_modes_inter_tables *tables, const 
                                     int32_t mi_stride);
 /* bools a picture emits at most: its 8x8 units times 111 (derived in csrc/modeinfo_inter_core.h) */
 uint32_t svt_hip_modes_inter_bools_capacity(int32_t width, int32_t height);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * MV-reference derivation: the grid of an inter picture -> the MV references and mode contexts the inter mode-info entry above takes
+ * as inputs, and the NEARESTMV / NEARMV candidates of every block.
+ *
+ * Replaces eb_vp9_find_mv_refs (VPX/vp9_mvref_common.c:20-197 with the tables and macros of vp9_mvref_common.h) as
+ * prepare_fast_loop_candidates calls it per block of 8x8 or larger and per reference frame of a picture that is not intra-only
+ * (Codec/EbModeDecision.c:638-672), and with it the filling of mbmi_ext->ref_mvs[..][0] and mbmi_ext->mode_context[..]: the eight
+ * positions of the block's size (mv_ref_blocks), the counter of the two nearest (mode_2_counter, counter_to_context), same-reference
+ * candidates first, then -- unless cm->use_prev_frame_mvs restricts the derivation -- other references' MVs with the sign inversion
+ * of scale_mv, and clamp_mv_ref.  Spatial candidates only, as in the reference; one tile.  Every position lies above or left of the
+ * block, so the derivation is a function of the grid (csrc/mvrefs_core.h) and runs per leaf in parallel.  Chain: encode pass ->
+ * tokeniser -> this -> inter mode info -> bool coder on one context's stream, no host round trip: d_ext_out is the d_ext of
+ * svt_hip_modes_inter_batch_device. */
+typedef struct svt_mvref_cand {             /* 32 bytes */
+    int16_t mv_row[3][2], mv_col[3][2];     /* [ref_frame - 1][candidate], clamped as the reference clamps them */
+    uint8_t count[3];                       /* eb_vp9_find_mv_refs' return value 0 / 1 / 2; 0xFF: not asked for in ref_mask */
+    uint8_t mode_context;
+    uint8_t pad_[4];
+} svt_mvref_cand;
+/* one picture of a batch; every pointer is a device pointer (host pointers in the host form); the grids share one mi_stride.
+ *   d_lf_mi, d_mc_mi   sb_type and is_inter; mv_row / mv_col of ref 0 / 1 (every unit of a block carries them; not read for an intra unit)
+ *   d_ext       ref_frame of every unit, mode at leaf origins; the other fields are not read
+ *   d_ext_out   WRITTEN (unless NULL), one complete record per unit of the picture: ref_frame as in d_ext; at a leaf's origin its mode;
+ *               at an inter leaf's origin ref_mv_row / ref_mv_col[k] = the first candidate of ref_frame[k] and mode_context; every
+ *               other field 0.  Must not alias d_ext
+ *   d_cand      WRITTEN (unless NULL), one record per unit: at the origin of a leaf of 8x8 or larger, intra leaves included as in the
+ *               reference, both candidates and the return value of every reference frame of ref_mask (an entry the reference does
+ *               not find is 0) and the mode context; at every other unit 0 with the three counts 0xFF
+ *   d_status    WRITTEN always: {inter leaves whose coded MVs contradict their mode -- NEARESTMV with an MV that is not the first
+ *               candidate of its reference, NEARMV not the second, ZEROMV not zero --, inter leaves}; both SVT_MODES_BAD_GRID for a grid
+ *               this entry does not take: a rectangular sb_type, a block that crosses the picture edge or overlaps another, a
+ *               reference frame above 3, is_inter, d_mc_mi's ref_list and ref_frame disagreeing about inter or compound, an inter block
+ *               below 8x8, an inter mode outside 10 .. 13.  d_ext_out and d_cand are then unspecified
+ *   ref_mask    bits 1 .. 3: the reference frames of d_cand
+ *   restrict_ref_mvs   cm->use_prev_frame_mvs: same-reference candidates only, at most one is returned unless two are found */
+typedef struct svt_mvrefs_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const svt_mc_mode_info *d_mc_mi;
+    const svt_mi_inter_ext *d_ext;
+    svt_mi_inter_ext       *d_ext_out;
+    svt_mvref_cand         *d_cand;
+    uint32_t               *d_status;
+    uint8_t                 ref_mask;
+    uint8_t                 restrict_ref_mvs;
+    uint8_t                 ref_frame_sign_bias[4];
+    uint8_t                 pad_[2];
+} svt_mvrefs_picture;                       /* 56 bytes */
+/* n_pics (<= 32) pictures of one geometry (multiples of 8, 8 .. 8192, mi_stride >= width / 8) in one call; their parameters may
+ * differ.  Asynchronous on the context's stream, no synchronisation.  Refused: a null required pointer, n_pics outside 1 .. 32, ref_mask
+ * with bit 0 or bits 4 .. 7 set, d_ext_out == d_ext. */
+int32_t svt_hip_mvrefs_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_mvrefs_picture *pics, int32_t width, int32_t height, int32_t mi_stride);
+/* host form of the same text (csrc/mvrefs_core.h), pure CPU, host pointers */
+int32_t svt_hip_mvrefs_picture(const svt_mvrefs_picture *pic, int32_t width, int32_t height, int32_t mi_stride);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.

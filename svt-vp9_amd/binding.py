@@ -202,6 +202,16 @@ class ModesInterPicture(C.Structure):
                 ("ref_frame_sign_bias", C.c_uint8 * 4), ("pad2_", C.c_uint8 * 7)]
 
 
+# MV-reference derivation (svt_mvref_cand / svt_mvrefs_picture of include/svtvp9_hip.h)
+MVREF_CAND_DTYPE = np.dtype([("mv_row", "<i2", (3, 2)), ("mv_col", "<i2", (3, 2)), ("count", "u1", (3,)), ("mode_context", "u1"), ("pad", "u1", (4,))])
+assert MVREF_CAND_DTYPE.itemsize == 32
+
+
+class MvrefsPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_mc_mi", C.c_void_p), ("d_ext", C.c_void_p), ("d_ext_out", C.c_void_p), ("d_cand", C.c_void_p), ("d_status", C.c_void_p),
+                ("ref_mask", C.c_uint8), ("restrict_ref_mvs", C.c_uint8), ("ref_frame_sign_bias", C.c_uint8 * 4), ("pad_", C.c_uint8 * 2)]
+
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -236,6 +246,7 @@ EXPORTS = [
     "svt_hip_boolcode_geometry",
     "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
     "svt_hip_modes_inter_set_tables", "svt_hip_modes_inter_batch_device", "svt_hip_modes_inter_picture", "svt_hip_modes_inter_bools_capacity",
+    "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
 ]
 
 _lib = None

@@ -1,0 +1,95 @@
+/*
+ * mvrefs_emu.cpp -- csrc/mvrefs.hip itself (kernels and entry point, included below) on the CPU through the stand-in runtime of
+ * hip/hip_runtime.h, compared with svt_hip_mvrefs_picture: every byte of d_ext_out and d_cand with the guard bytes behind them, and the
+ * status words (the two buffers are left out of the comparison for a grid the stage does not take: their contents are unspecified).
+ * argv[1]: a file holding int32 n_groups; per group int32 width, height, mi_stride, n_pics, then per picture 8 bytes (ref_mask,
+ * restrict_ref_mvs, ref_frame_sign_bias[4], d_ext_out wanted, d_cand wanted) and the three grids (mi_rows x mi_stride records each:
+ * svt_lf_mode_info, svt_mc_mode_info, svt_mi_inter_ext).  A group is one batch call.
+ */
+#include "mvrefs.hip"
+#include <stdio.h>
+thread_local dim3 threadIdx, blockIdx, blockDim;
+pthread_barrier_t *g_bar, *g_wave_bar;
+long long g_shfl[1024];
+void emu_launch(dim3 grid, dim3 block, std::function<void()> body) {
+    pthread_barrier_t bar, wave[16];
+    pthread_barrier_init(&bar, nullptr, block.x);
+    for (unsigned w = 0; w < (block.x + 63) / 64; w++) pthread_barrier_init(&wave[w], nullptr, block.x - 64 * w < 64 ? block.x - 64 * w : 64);
+    g_bar = &bar; g_wave_bar = wave;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < block.x; t++) th.emplace_back([=] {
+        blockDim = block; threadIdx = dim3(t);
+        for (unsigned by = 0; by < grid.y; by++) for (unsigned bx = 0; bx < grid.x; bx++) { blockIdx = dim3(bx, by); body(); pthread_barrier_wait(g_bar); }
+    });
+    for (auto &t : th) t.join();
+    pthread_barrier_destroy(&bar);
+}
+int32_t svt_set_error(int32_t c, const char *m) { fprintf(stderr, "error %d %s\n", c, m); return c; }
+int32_t svt_set_hip_error(hipError_t e, const char *f, int l) { return -1; }
+static char stage_h[65536], stage_d[65536];
+int svt_ctx_stage(svt_hip_ctx *, size_t n, void **h, void **d) { *h = stage_h; *d = stage_d; return n > sizeof stage_h; }
+void svt_ctx_stage_commit(svt_hip_ctx *) {}
+void *svt_ctx_slot(svt_hip_ctx *c, int s, size_t bytes) {
+    if (bytes > c->slot_bytes[s]) { free(c->slot[s]); hipMalloc(&c->slot[s], bytes); c->slot_bytes[s] = bytes; }
+    return c->slot[s];
+}
+#define GUARD 64
+struct pic_bufs {
+    std::vector<svt_lf_mode_info> mi;
+    std::vector<svt_mc_mode_info> mc;
+    std::vector<svt_mi_inter_ext> ext;
+    std::vector<uint32_t> ext_out[2], status[2]; /* (4-byte aligned, as the device's buffers are) */
+    std::vector<uint4> cand[2];
+    uint8_t par[8];
+    svt_mvrefs_picture desc(int k) {
+        svt_mvrefs_picture d;
+        memset(&d, 0, sizeof d);
+        d.d_lf_mi = mi.data(); d.d_mc_mi = mc.data(); d.d_ext = ext.data();
+        d.d_ext_out = par[6] ? (svt_mi_inter_ext *)ext_out[k].data() : nullptr; d.d_cand = par[7] ? (svt_mvref_cand *)cand[k].data() : nullptr;
+        d.d_status = status[k].data();
+        d.ref_mask = par[0]; d.restrict_ref_mvs = par[1];
+        memcpy(d.ref_frame_sign_bias, par + 2, 4);
+        return d;
+    }
+};
+int main(int argc, char **argv) {
+    static svt_hip_ctx ctx;
+    FILE *f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
+    int32_t n_groups = 0;
+    if (!f || fread(&n_groups, 4, 1, f) != 1) return 2;
+    int bad = 0;
+    for (int g = 0; g < n_groups; g++) {
+        int32_t whn[4];
+        if (fread(whn, 4, 4, f) != 4) return 3;
+        const int W = whn[0], H = whn[1], stride = whn[2], n_pics = whn[3], units = stride * (H / 8);
+        std::vector<pic_bufs> P(n_pics);
+        std::vector<svt_mvrefs_picture> d(n_pics);
+        for (int i = 0; i < n_pics; i++) {
+            pic_bufs &p = P[i];
+            p.mi.resize(units); p.mc.resize(units); p.ext.resize(units);
+            if (fread(p.par, 1, 8, f) != 8 || fread(p.mi.data(), 8, units, f) != (size_t)units || fread(p.mc.data(), 12, units, f) != (size_t)units ||
+                fread(p.ext.data(), 12, units, f) != (size_t)units)
+                return 4;
+            for (int k = 0; k < 2; k++) {
+                p.ext_out[k].assign(3 * (size_t)units + GUARD, 0xA5A5A5A5u); p.status[k].assign(2 + GUARD, 0x77777777u);
+                p.cand[k].assign(2 * (size_t)units + GUARD, make_uint4(0x5A5A5A5Au, 0x5A5A5A5Au, 0x5A5A5A5Au, 0x5A5A5A5Au));
+            }
+            d[i] = p.desc(0);
+        }
+        const int r1 = svt_hip_mvrefs_batch_device(&ctx, n_pics, d.data(), W, H, stride);
+        for (int i = 0; i < n_pics; i++) {
+            pic_bufs &p = P[i];
+            svt_mvrefs_picture h = p.desc(1);
+            const int  r2 = svt_hip_mvrefs_picture(&h, W, H, stride);
+            const bool taken = p.status[1][0] != SVT_MODES_BAD_GRID;
+            bool       ok = !r1 && !r2 && p.status[0] == p.status[1];
+            if (taken) ok = ok && p.ext_out[0] == p.ext_out[1] && !memcmp(p.cand[0].data(), p.cand[1].data(), sizeof(uint4) * p.cand[0].size());
+            for (int k = 0; k < GUARD; k++) ok = ok && p.ext_out[0][3 * (size_t)units + k] == 0xA5A5A5A5u && p.cand[0][2 * (size_t)units + k].x == 0x5A5A5A5Au;
+            printf("group %d %dx%d stride %d picture %d status %u/%u %u/%u %s\n", g, W, H, stride, i, p.status[0][0], p.status[1][0], p.status[0][1], p.status[1][1],
+                   ok ? "ok" : "MISMATCH");
+            bad += !ok;
+        }
+    }
+    printf("bad %d\n", bad);
+    return bad;
+}
