@@ -596,7 +596,12 @@ typedef struct svt_lf_mode_info {
 int32_t svt_hip_lf_build_masks(const svt_lf_mode_info *mi, int32_t mi_stride, int32_t mi_rows, int32_t mi_cols,
                                svt_lf_mask *lfm, int32_t lfm_stride);
 
-/* 4:2:0 recon picture, planes filtered in place. */
+/* 4:2:0 recon picture, planes filtered in place.  For the svt_hip_lf_* entry points: y, u, v, y_stride and uv_stride must be multiples
+ * of 4 (u, v and uv_stride are not looked at when y_only is set), otherwise the call returns SVT_HIP_ERR_BAD_PARAMETER and launches
+ * nothing.  No further alignment is needed: a stride may be larger than the width and sample (0, 0) may lie anywhere inside a padded
+ * picture; only the width x height luma and width/2 x height/2 chroma samples are read or written.  Addresses, strides and widths
+ * that are all multiples of 8 get the faster 8-byte copies.  Every size from one 8x8 block up is accepted, pictures one block high
+ * or wide included. */
 typedef struct svt_yuv_planes {
     uint8_t *y, *u, *v;    /* pointers to picture sample (0,0) of each plane */
     int32_t  y_stride, uv_stride;
@@ -609,7 +614,8 @@ int32_t svt_hip_lf_reserve(svt_hip_ctx *ctx, int32_t n_pics, int32_t mi_rows, in
 
 /* = eb_vp9_loop_filter_frame(frame, cm, xd, lfm_base, filter_level, y_only=0, partial=0)
  * (VPX/vp9_loopfilter.c:1521-1546 -> loop_filter_rows :1456).  lfm: one mask per SB in raster order
- * [ceil(mi_rows/8)][lfm_stride].  Device pointers.  mi_rows/mi_cols in 8x8 units. */
+ * [ceil(mi_rows/8)][lfm_stride].  Device pointers.  mi_rows/mi_cols in 8x8 units; d_recon->width / height must equal mi_cols * 8 /
+ * mi_rows * 8, and the planes must meet svt_yuv_planes' alignment rule -- SVT_HIP_ERR_BAD_PARAMETER otherwise. */
 int32_t svt_hip_lf_frame_device(svt_hip_ctx *ctx, const svt_yuv_planes *d_recon, const svt_lf_mask *d_lfm,
                                 int32_t lfm_stride, const svt_lf_thresh *thr, int32_t mi_rows, int32_t mi_cols,
                                 int32_t y_only);

@@ -33,6 +33,25 @@ int32_t svt_oracle_tq_batch(const uint8_t *src, const uint8_t *pred, uint8_t *re
 /* L2: eb_vp9_build_mask_frame / eb_vp9_setup_mask (VPX/vp9_loopfilter.c:901-1040, 1548-1571) */
 int32_t svt_oracle_lf_build_masks(const svt_lf_mode_info *mi, int32_t mi_stride, int32_t mi_rows, int32_t mi_cols,
                                   svt_lf_mask *lfm, int32_t lfm_stride);
+/* Census of svt_oracle_lf_frame: which branches of the edge filters, of the two edge walks and of adjust_mask the oracle
+ * takes on a picture -- the tests use it to prove that their inputs reach a branch.  The slots (tests/svt_testlib.py reads
+ * this enum): per sample position, the outcome of an edge of width 4 / 8 / 16 that did not take a flat filter (mask off,
+ * filter4 with hev, filter4 without hev), the flat filters, and the clamps of filter4 that changed a value -- counted only
+ * where the clamped value reaches the output (mask on; hev on for ps1 - qs1); per edge, the two [quirk]s of oracle_lf.c with
+ * differing levels; per SB, the ragged branches of adjust_mask. */
+enum svt_oracle_lf_census_slot {
+    SVT_LFC_W4_MASK_OFF, SVT_LFC_W4_FILTER4_HEV, SVT_LFC_W4_FILTER4_NO_HEV,
+    SVT_LFC_W8_MASK_OFF, SVT_LFC_W8_FILTER4_HEV, SVT_LFC_W8_FILTER4_NO_HEV,
+    SVT_LFC_W16_MASK_OFF, SVT_LFC_W16_FILTER4_HEV, SVT_LFC_W16_FILTER4_NO_HEV,
+    SVT_LFC_FLAT8_W8, SVT_LFC_FLAT8_W16, SVT_LFC_FLAT16,
+    SVT_LFC_SAT_PS1_QS1, SVT_LFC_SAT_F_3D, SVT_LFC_F_PLUS4_OVER_127, SVT_LFC_SAT_Q0_OUT, SVT_LFC_SAT_P0_OUT,
+    SVT_LFC_VERT16_PAIR_LEVELS_DIFFER, SVT_LFC_HORIZ16_PAIR_LEVELS_DIFFER,
+    SVT_LFC_ROWS_1, SVT_LFC_ROWS_5, SVT_LFC_COLS_1, SVT_LFC_COLS_5,
+    SVT_LFC_COUNT
+};
+/* counts[SVT_LFC_COUNT] is bumped by every svt_oracle_lf_frame from now on; NULL (the default) turns the census off.  Not
+ * thread-safe.  The filtered samples are the same with the census on or off. */
+void svt_oracle_lf_census(uint64_t *counts);
 /* T3: full_distortion_kernel32bit (C_DEFAULT/EbPictureOperators_C.c:288-311) and the batch with distortions */
 void    svt_oracle_full_distortion32(const int16_t *coeff, const int16_t *recon_coeff, int32_t count, uint64_t out[2]);
 int32_t svt_oracle_tq_batch_dist(const uint8_t *src, const uint8_t *pred, uint8_t *recon, const svt_tq_block *blocks,

@@ -22,6 +22,24 @@
 static inline int iabs(int v) { return v < 0 ? -v : v; }
 static inline int8_t sclamp(int t) { return (int8_t)(t < -128 ? -128 : t > 127 ? 127 : t); }
 
+/* opt-in census (oracle.h): counters only, no value below depends on them */
+static uint64_t *lf_census;
+void svt_oracle_lf_census(uint64_t *counts) { lf_census = counts; }
+#define CENSUS(slot) do { if (lf_census) lf_census[slot]++; } while (0)
+static inline int sat8(int t) { return t < -128 || t > 127; }
+/* filter4 of one position, restated in plain ints from its inputs: which outcome, and which clamps changed a value */
+static void census_filter4(int kind, int mask, int hev, int ps1, int ps0, int qs0, int qs1) {
+    if (!lf_census) return;
+    lf_census[(kind == 16 ? SVT_LFC_W16_MASK_OFF : kind == 8 ? SVT_LFC_W8_MASK_OFF : SVT_LFC_W4_MASK_OFF) + (!mask ? 0 : hev ? 1 : 2)]++;
+    if (!mask) return;
+    if (hev && sat8(ps1 - qs1)) lf_census[SVT_LFC_SAT_PS1_QS1]++;
+    const int f0 = hev ? sclamp(ps1 - qs1) : 0, f = sclamp(f0 + 3 * (qs0 - ps0));
+    if (sat8(f0 + 3 * (qs0 - ps0))) lf_census[SVT_LFC_SAT_F_3D]++;
+    if (f + 4 > 127) lf_census[SVT_LFC_F_PLUS4_OVER_127]++;
+    if (sat8(qs0 - (sclamp(f + 4) >> 3))) lf_census[SVT_LFC_SAT_Q0_OUT]++;
+    if (sat8(ps0 + (sclamp(f + 3) >> 3))) lf_census[SVT_LFC_SAT_P0_OUT]++;
+}
+
 /* one pixel position across an edge: p[-k*st] = p(k-1).., p[k*st] = q(k) ; kind 4 / 8 / 16 */
 static void filter_px(uint8_t *s, int st, int kind, int mblim, int lim, int hev_thr) {
     const int p3 = s[-4 * st], p2 = s[-3 * st], p1 = s[-2 * st], p0 = s[-st];
@@ -55,6 +73,7 @@ static void filter_px(uint8_t *s, int st, int kind, int mblim, int lim, int hev_
             s[5 * st]  = R4(p1 + p0 + q0 + q1 + q2 + q3 + q4 + q5 * 2 + q6 + q7 * 6);
             s[6 * st]  = R4(p0 + q0 + q1 + q2 + q3 + q4 + q5 + q6 * 2 + q7 * 7);
 #undef R4
+            CENSUS(SVT_LFC_FLAT16);
             return;
         }
     }
@@ -67,6 +86,7 @@ static void filter_px(uint8_t *s, int st, int kind, int mblim, int lim, int hev_
         s[1 * st]  = R3(p1 + p0 + q0 + 2 * q1 + q2 + q3 + q3);
         s[2 * st]  = R3(p0 + q0 + q1 + 2 * q2 + q3 + q3 + q3);
 #undef R3
+        CENSUS(kind == 16 ? SVT_LFC_FLAT8_W16 : SVT_LFC_FLAT8_W8);
         return;
     }
     /* filter4 (int8 arithmetic, mask/hev as 0 / -1) */
@@ -81,6 +101,7 @@ static void filter_px(uint8_t *s, int st, int kind, int mblim, int lim, int hev_
     f = (int8_t)(((f1 + 1) >> 1) & ~hev);
     s[st]      = (uint8_t)(sclamp(qs1 - f) ^ 0x80);
     s[-2 * st] = (uint8_t)(sclamp(ps1 + f) ^ 0x80);
+    census_filter4(kind, mask, hev, ps1, ps0, qs0, qs1);
 }
 
 /* `count` pixels along an edge; across = step across the edge, along = step along it */
@@ -118,6 +139,8 @@ static void adjust_mask(svt_lf_mask *m, int mi_row, int mi_col, int mi_rows, int
         const uint16_t muv = (uint16_t)(((uint16_t)1 << (((rows + 1) >> 1) << 2)) - 1);
         for (int i = 0; i < 3; i++) { m->left_y[i] &= my; m->above_y[i] &= my; m->left_uv[i] &= muv; m->above_uv[i] &= muv; }
         m->int_4x4_y &= my; m->int_4x4_uv &= muv;
+        if (rows == 1) CENSUS(SVT_LFC_ROWS_1);
+        if (rows == 5) CENSUS(SVT_LFC_ROWS_5);
         if (rows == 1) { m->above_uv[1] |= m->above_uv[2]; m->above_uv[2] = 0; }
         if (rows == 5) { m->above_uv[1] |= m->above_uv[2] & 0xff00; m->above_uv[2] &= (uint16_t)~(m->above_uv[2] & 0xff00); }
     }
@@ -128,6 +151,8 @@ static void adjust_mask(svt_lf_mask *m, int mi_row, int mi_col, int mi_rows, int
         const uint16_t muvi = (uint16_t)(((1 << (cols >> 1)) - 1) * 0x1111);
         for (int i = 0; i < 3; i++) { m->left_y[i] &= my; m->above_y[i] &= my; m->left_uv[i] &= muv; m->above_uv[i] &= muv; }
         m->int_4x4_y &= my; m->int_4x4_uv &= muvi;
+        if (cols == 1) CENSUS(SVT_LFC_COLS_1);
+        if (cols == 5) CENSUS(SVT_LFC_COLS_5);
         if (cols == 1) { m->left_uv[1] |= m->left_uv[2]; m->left_uv[2] = 0; }
         if (cols == 5) { m->left_uv[1] |= (m->left_uv[2] & 0xcccc); m->left_uv[2] &= (uint16_t)~(m->left_uv[2] & 0xcccc); }
     }
@@ -150,6 +175,7 @@ static void vert_row2(int ss, uint8_t *s, int pitch, unsigned m16, unsigned m8, 
             const int l[2] = {lfl[0], lfl[fwd]};
             uint8_t  *r[2] = {s, s + 8 * pitch};
             int       n[2] = {rows_avail < 8 ? rows_avail : 8, rows_avail - 8 < 0 ? 0 : rows_avail - 8 < 8 ? rows_avail - 8 : 8};
+            if ((m16 & one) == one && l[0] != l[1]) CENSUS(SVT_LFC_VERT16_PAIR_LEVELS_DIFFER);
             if (m16 & one) {
                 if ((m16 & one) == one) oracle_lpf_edge(r[0], 1, pitch, n[0] + n[1], 16, t->mblim[l[0]], t->lim[l[0]], t->hev_thr[l[0]]);
                 else { int h = !(m16 & 1); oracle_lpf_edge(r[h], 1, pitch, n[h], 16, t->mblim[l[h]], t->lim[l[h]], t->hev_thr[l[h]]); }
@@ -183,6 +209,7 @@ static void horiz_row(uint8_t *s, int pitch, unsigned m16, unsigned m8, unsigned
         count = 1;
         if (mask & 1) {
             const int l0 = lfl[0];
+            if ((m16 & 3) == 3 && l0 != lfl[1]) CENSUS(SVT_LFC_HORIZ16_PAIR_LEVELS_DIFFER);
             if (m16 & 1) {
                 if ((m16 & 3) == 3) { HEDGE(s, 0, 16, l0); HEDGE(s + 8, 8, 16, l0); count = 2; }
                 else HEDGE(s, 0, 16, l0);

@@ -297,7 +297,8 @@ __device__ __forceinline__ void lf_line(uint8_t *s, int st, int nblk, const uint
  * Rows with seam[ty] != 0 belong to a seam between two SB rows: they are written by one workgroup and read by the
  * workgroup of the next SB row inside the same launch, so they move with agent-scope (sc1, write-through / L2-bypass)
  * 8-byte accesses -- no release/acquire fence is needed for them (cdna_hip_programming.md, guideline 16).  Up to UNITS
- * loads per lane are in flight before the first store.  Plane rows must be 8-byte (wide) or 4-byte aligned. */
+ * loads per lane are in flight before the first store.  Plane rows must be 8-byte (wide) or 4-byte aligned, and nx a multiple of the
+ * unit: the caller picks the 8-byte unit only for planes whose every copied width is a multiple of 8 (wide_y / wide_c). */
 /* t / nu for the tile copies (units per tile row: at most 18): reciprocals from constant memory, one v_mul_hi per unit instead
  * of an integer division (~25 instructions) -- the copy waves spent most of their instructions dividing */
 struct lf_magic_table {
@@ -461,8 +462,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int mi_row = sb_row * 8;
     const int wave = tid >> 6, lane = tid & 63;
     const int nrows = P.mi_rows - mi_row < 8 ? P.mi_rows - mi_row : 8; /* 8-row bands of this SB row */
-    const bool wide_y = (((uintptr_t)P.planes.y | (uintptr_t)P.planes.y_stride) & 7) == 0;
-    const bool wide_c = (((uintptr_t)P.planes.u | (uintptr_t)P.planes.v | (uintptr_t)P.planes.uv_stride) & 7) == 0;
+    /* 8-byte copy units need more than 8-byte aligned rows: tile_io_t moves nx / 8 units per row, and a chroma width of 4 modulo 8
+     * (W = 72, 136, 200, ...) leaves 4 or 12 columns in the last SB -- those planes take 4-byte units whatever their alignment */
+    const bool wide_y = (((uintptr_t)P.planes.y | (uintptr_t)P.planes.y_stride | (uintptr_t)W) & 7) == 0;
+    const bool wide_c = (((uintptr_t)P.planes.u | (uintptr_t)P.planes.v | (uintptr_t)P.planes.uv_stride | (uintptr_t)(W >> 1)) & 7) == 0;
     unsigned long long tm_ = prof ? __builtin_amdgcn_s_memtime() : 0;
     const bool rowts = prof && job % n_pics == 0 && sb_row < 64;
 #define LF_ROWTS(k, who, cond) do { if (rowts && tid == (who) && (cond)) g_lf_rowts[sb_row][k] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -607,6 +610,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 } // namespace
 
+/* Alignment contract (svtvp9_hip.h): every plane address and stride a multiple of 4, nothing else.  Strides may exceed the width and
+ * sample (0, 0) may sit anywhere inside a larger buffer; only bytes inside width x height (width / 2 x height / 2) are read or written.
+ * A plane is copied in 8-byte units when its address, its stride and its width are all multiples of 8, in 4-byte units otherwise. */
 static int32_t lf_launch(svt_hip_ctx *ctx, int n_pics, const svt_yuv_planes *d_recon, const svt_lf_mask *const *d_lfm, const int32_t *lfm_stride,
                          const svt_lf_thresh *thr, const int32_t *mi_rows, const int32_t *mi_cols, int32_t y_only) {
     int max_rows = 0, max_cols = 0;

@@ -70,6 +70,19 @@ def gen_lf():
     np.savez_compressed(os.path.join(G, "lf_reference.npz"), **lf)
 
 
+def gen_lf_extremes():
+    # ---- LF on the extremes list (svt_testlib.LF_EXTREMES_CASES): the reference's planes, which the oracle must already equal ----
+    lf = {}
+    for c in T.LF_EXTREMES_CASES:
+        case = T.make_lf_extremes_case(*c)
+        ref = T.ref_lf_frame(case)
+        assert all(np.array_equal(a, b) for a, b in zip(T.oracle_lf_frame(case), ref)), c
+        assert all(np.array_equal(a, b) for a, b in zip(T.oracle_lf_frame(case, True), T.ref_lf_frame(case, True))), c
+        for n, a in zip("yuv", ref):
+            lf[n + "|" + T.lf_extremes_key(c)] = a
+    np.savez_compressed(os.path.join(G, "lf_extremes_reference.npz"), **lf)
+
+
 def gen_lf_masks():
     # ---- LF masks: reference eb_vp9_setup_mask on random mode-info grids (same cases as tests/test_lf_masks.py) ----
     lm = {}
@@ -183,7 +196,7 @@ def gen_encdec_flags():
     np.savez_compressed(os.path.join(G, "encdec_flags_reference.npz"), flags=T.ref_encdec_flags())
 
 
-SECTIONS = ("scan", "me", "tq", "lf", "lf_masks", "mc", "rate", "quant", "ivf", "lf_params", "me_presets", "sad_loop", "sb_stats", "api", "refpad", "avg_ssd", "pd_split", "encdec_flags", "qp_scaling")
+SECTIONS = ("scan", "me", "tq", "lf", "lf_extremes", "lf_masks", "mc", "rate", "quant", "ivf", "lf_params", "me_presets", "sad_loop", "sb_stats", "api", "refpad", "avg_ssd", "pd_split", "encdec_flags", "qp_scaling")
 
 
 def main():

@@ -653,6 +653,75 @@ def oracle_lf_frame(case, y_only=False):
     return y, u, v
 
 
+def _lf_census_slots():
+    """the slot names of enum svt_oracle_lf_census_slot, in order, read from oracle/oracle.h (one definition for both sides)"""
+    import re
+    body = re.search(r"enum svt_oracle_lf_census_slot \{(.*?)\}", open(os.path.join(ORACLE_DIR, "oracle.h")).read(), re.S).group(1)
+    names = re.findall(r"SVT_LFC_(\w+)", body)
+    assert names[-1] == "COUNT"
+    return tuple(names[:-1])
+
+
+LF_CENSUS = _lf_census_slots()
+# per sample position / per edge / per SB (oracle.h)
+LF_CENSUS_PER_POSITION = LF_CENSUS[:LF_CENSUS.index("VERT16_PAIR_LEVELS_DIFFER")]
+
+
+def oracle_lf_frame_census(case, y_only=False):
+    """oracle_lf_frame with the oracle's census switched on for this one call: (planes, {slot name: count})"""
+    counts = (C.c_uint64 * len(LF_CENSUS))()
+    oracle().svt_oracle_lf_census(counts)
+    try:
+        planes = oracle_lf_frame(case, y_only)
+    finally:
+        oracle().svt_oracle_lf_census(None)
+    return planes, dict(zip(LF_CENSUS, (int(c) for c in counts)))
+
+
+_LF_WALK_SCALES = (1, 1, 4, 24, 63)
+_LF_WALK_STARTS = (0, 3, 128, 252, 255)
+
+
+def make_lf_extremes_case(seed, w, h, sharpness, axis):
+    """Deblocking input for the branches make_lf_case does not reach: every plane is a set of independent random walks, down
+    the columns (axis 0: smooth across horizontal edges, unrelated neighbours across vertical ones) or along the rows (axis 1).
+    A walk starts at one of _LF_WALK_STARTS, steps uniformly in [-s, s] with s drawn per 16-sample segment from _LF_WALK_SCALES,
+    and is reflected at 0 and 255: s = 1 gives the runs within +-1 that the 8- and 15-tap filters need, s = 63 next to the
+    range ends the differences at which filter4's int8 clamps act.  The masks carry mostly level 63 (lim 63 at sharpness 0)."""
+    rng = np.random.default_rng(seed)
+
+    def plane(pw, ph):
+        n, lines = (ph, pw) if axis == 0 else (pw, ph)
+        scale = np.repeat(rng.choice(_LF_WALK_SCALES, ((n + 15) // 16, lines)), 16, axis=0)[:n]
+        step = np.floor(rng.random((n, lines)) * (2 * scale + 1)).astype(np.int64) - scale
+        step[0] = rng.choice(_LF_WALK_STARTS, lines)
+        pos = np.cumsum(step, axis=0) % 510
+        pos = np.where(pos > 255, 510 - pos, pos).astype(np.uint8)
+        return np.ascontiguousarray(pos if axis == 0 else pos.T)
+
+    y, u, v = plane(w, h), plane(w // 2, h // 2), plane(w // 2, h // 2)
+    mi_rows, mi_cols = h // 8, w // 8
+    lfm = gen_lf_masks(rng, (mi_rows + 7) // 8, (mi_cols + 7) // 8, level_choices=(63, 63, 40, 1))
+    thr = B.LfThresh()
+    oracle().svt_oracle_lf_thresh_init(C.byref(thr), sharpness)
+    return dict(y=y, u=u, v=v, lfm=lfm, thr=thr, mi_rows=mi_rows, mi_cols=mi_cols, sharpness=sharpness, axis=axis)
+
+
+# (seed, w, h, sharpness, axis): the fixed list behind tests/golden/lf_extremes_reference.npz and every test of the extremes.
+# Sizes: mi_cols = 33 / 29 and mi_rows = 25 / 21 leave 1 or 5 blocks in the last SB column / row; 104x40, 40x104 and the
+# one-block-high / -wide pictures do so inside a single SB row / column.  tests/test_lf_census.py holds the list to the
+# branch counts it is there for; the seeds were picked among the first few hundred for those counts (filter4's clamps act about ten
+# times per picture of this size, and only at sharpness 0 with level 63).
+LF_EXTREMES_CASES = (
+    (51, 264, 200, 0, 0), (575, 232, 200, 0, 1), (27, 264, 168, 3, 1), (10, 232, 168, 7, 0),
+    (185, 104, 40, 0, 1), (6, 40, 104, 0, 0), (7, 72, 8, 3, 1), (8, 8, 72, 7, 0),
+)
+
+
+def lf_extremes_key(c):
+    return "|".join(str(v) for v in c)
+
+
 def ref_lf_frame(case, y_only=False):
     exe = os.path.join(REF_DIR, "ref_lf_frame")
     # the reference filters whole 8-sample groups and relies on the recon buffer's padding where a chroma block is

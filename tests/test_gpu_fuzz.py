@@ -24,7 +24,8 @@ def test_me_ceiling_sweep():
 
 
 def test_lf_random_sweep():
-    """tools/lf_fuzz.py: random sizes, masks, levels, sharpness 0..7, noisy and smooth (flat-filter) content"""
+    """tools/lf_fuzz.py: random sizes, masks, levels, sharpness 0..7, noisy, smooth (flat-filter) and random-walk (15-tap, clamps) content,
+    a random padded stride per plane whose padding must survive"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lf_fuzz.py"), "60", "5"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 

@@ -46,6 +46,17 @@ def test_lf_oracle_matches_reference_golden():
         assert np.array_equal(y, g["y|" + k]) and np.array_equal(u, g["u|" + k]) and np.array_equal(v, g["v|" + k])
 
 
+def test_lf_extremes_oracle_matches_reference_golden():
+    """the reference's own planes for svt_testlib.LF_EXTREMES_CASES (random-walk content: 15-tap filter, filter4's clamps, both
+    16-wide pair quirks, ragged SBs -- tests/test_lf_census.py), which lf_reference.npz's pictures do not reach"""
+    g = _golden("lf_extremes_reference.npz")
+    assert sorted({k.split("|", 1)[1] for k in g}) == sorted(T.lf_extremes_key(c) for c in T.LF_EXTREMES_CASES)
+    for c in T.LF_EXTREMES_CASES:
+        k = T.lf_extremes_key(c)
+        for n, a in zip("yuv", T.oracle_lf_frame(T.make_lf_extremes_case(*c))):
+            assert np.array_equal(a, g[n + "|" + k]), (c, n, int(np.sum(a != g[n + "|" + k])), np.argwhere(a != g[n + "|" + k])[:6].tolist())
+
+
 @pytest.mark.parametrize("seed", [1, 2])
 def test_avg_ssd_oracle_matches_reference_golden(seed):
     """eb_vp9_combined_averaging_ssd (Codec/EbMotionEstimation.c:1708-1725), the quarter-pel metric of the SSD fractional
@@ -138,6 +149,18 @@ def test_lf_frame_vs_reference(w, h, seed, sharp):
     for y_only in (False, True):
         o, r = T.oracle_lf_frame(case, y_only), T.ref_lf_frame(case, y_only)
         assert all(np.array_equal(a, b) for a, b in zip(o, r))
+
+
+@live
+@pytest.mark.parametrize("c", T.LF_EXTREMES_CASES, ids=T.lf_extremes_key)
+def test_lf_extremes_vs_reference(c):
+    if not T.have_ref("ref_lf_frame"):
+        pytest.skip("ref_lf_frame not built")
+    case = T.make_lf_extremes_case(*c)
+    for y_only in (False, True):
+        o, r = T.oracle_lf_frame(case, y_only), T.ref_lf_frame(case, y_only)
+        for n, a, b in zip("yuv", o, r):
+            assert np.array_equal(a, b), (y_only, n, int(np.sum(a != b)), np.argwhere(a != b)[:6].tolist())
 
 
 @live
