@@ -746,7 +746,7 @@ int32_t svt_hip_coeff_rate_batch(svt_hip_ctx *ctx, const int16_t *qcoeff, size_t
  * every coded block in front of the bool coder (Codec/EbEntropyCodingProcess.c:381-398).  The reference codes with the default
  * probabilities (its count-based update is compiled out, VPX/vp9_tokenize.c:301-304), so a token stream plus the fixed tables is
  * all the arithmetic coder needs (the bool coder and the mode-info stages of key frames and of inter pictures follow below); the
- * headers and the packets stay on the host.
+ * two headers and the packets are the frame stage's (further below).
  *
  * One token = one uint32_t record: extra << 16 | prob_row << 4 | token.
  *   token     ZERO 0, ONE..FOUR 1..4, CAT1..CAT6 5..10 (|v| 5-6, 7-10, 11-18, 19-34, 35-66, >= 67), EOB 11 (at scan position eob
@@ -832,7 +832,8 @@ uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
  * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
  * uploaded once per context.  The raw bools and the segment list of a tile come from the mode-info stages below (key frames:
  * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device behind svt_hip_mvrefs_batch_device); the
- * uncompressed and compressed headers and packet delivery are not on the device. */
+ * uncompressed and compressed headers and the packet around the tile are the frame stage's (svt_hip_frame_header_host,
+ * svt_hip_frame_batch_device); delivery through libSvtVp9Enc.so is not here yet. */
 typedef struct svt_bool_tables {
     uint8_t coef_probs[576 * 3]; /* [prob_row][node]: cm->fc->coef_probs flattened */
     uint8_t pareto[255][8];      /* eb_vp9_pareto8_full */
@@ -948,7 +949,8 @@ uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height);
  * (VPX/vp9_pred_common.c) and is taken from the grid (csrc/modeinfo_inter_core.h).  Chain: encode pass -> tokeniser -> this -> bool
  * coder on one context's stream, no host round trip.  mbmi_ext's values -- the MV references and the mode context that
  * eb_vp9_find_mv_refs derives -- are inputs here exactly as they are inputs of pack_inter_mode_mvs; svt_hip_mvrefs_batch_device below
- * derives them on the device.  The two headers and packet delivery are not on the device.
+ * derives them on the device.  The two headers and the packet around the tile are the frame stage's (svt_hip_frame_header_host,
+ * svt_hip_frame_batch_device); delivery through libSvtVp9Enc.so is not here yet.
  *
  * The tables are the caller's data (the frame context cm->fc), uploaded once per context. */
 typedef struct svt_modes_mv_comp {       /* nmv_component (VPX/vp9_entropymv.h) */
@@ -1323,6 +1325,102 @@ void         svt_hip_device_set_destroy(svt_hip_device_set *set);
  * stream also waits for the copy, so the producer may overwrite d_src afterwards.  Peer access is enabled on first use;
  * the copy travels device to device (xGMI) when the devices are peers.  src == dst degenerates to a device-local copy. */
 int32_t svt_hip_ref_handoff_device(svt_hip_ctx *src, const void *d_src, svt_hip_ctx *dst, void *d_dst, size_t bytes);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Frame packets: the two VP9 headers (host) and the dense assembly of header || tile || trailer of a batch (device).
+ *
+ * Replaces eb_vp9_pack_bitstream (VPX/vp9_bitstream.c:1369-1412): write_uncompressed_header (:1186-1290), the 16-bit first_part_size,
+ * write_compressed_header (:1292-1367) and the copy of the entropy coder's tile bytes behind them; and the four one-byte
+ * show-existing frames Codec/EbPacketizationProcess.c:374-453 appends to a packet flagged EB_BUFFERFLAG_SHOW_EXT (svt_ivf_packetize
+ * below splits such a packet again).
+ *
+ * The no-update rule.  The reference keeps FRAME_COUNTS at zero: the increments of eb_vp9_tokenize_sb are compiled out
+ * (VPX/vp9_tokenize.c:405-425, "count-based probability update not yet supported"), tx_totals is never incremented, and
+ * Codec/EbResourceCoordinationProcess.c:666 clears the counts.  With zero counts update_coef_probs writes one 0 bit per transform size
+ * (tx_totals <= 20, VPX/vp9_bitstream.c:679-681), eb_vp9_cond_prob_diff_update finds no savings (VPX/vp9_subexp.c:173-185) and
+ * update_mv no gain (VPX/vp9_encodemv.c:144-155): every one of them writes a 0 at probability 252.  The compressed header is therefore
+ * a function of: intra-only or not, reference_mode, allow_comp_inter_inter, allow_hp -- and nothing in either header depends on device
+ * data, so the host writes both, first_part_size included, before the tile has been coded.
+ *
+ * Fixed, as in the reference: profile 0 (8 bit, 4:2:0), segmentation off, one tile (log2_tile_cols = log2_tile_rows = 0), tx_mode
+ * ALLOW_32X32, interpolation filter literal 0 (write_interp_filter(0, ..)), found = 0 in write_frame_size_with_refs. */
+typedef struct svt_frame_params {
+    /* frame state */
+    uint8_t frame_type;                 /* 0 KEY_FRAME, 1 INTER_FRAME */
+    uint8_t show_frame, error_resilient_mode, intra_only;
+    uint8_t reset_frame_context;        /* 0 .. 3 */
+    uint8_t refresh_frame_context, frame_parallel_decoding_mode;
+    uint8_t frame_context_idx;          /* 0 .. 3 */
+    /* references */
+    uint8_t refresh_frame_mask;         /* ref_signal.refresh_frame_mask */
+    uint8_t ref_dpb_index[3];           /* ref_signal.ref_dpb_index: LAST, GOLDEN, ALTREF; 0 .. 7 */
+    uint8_t ref_frame_sign_bias[4];     /* cm->ref_frame_sign_bias; [0] (INTRA_FRAME) is not coded */
+    uint8_t allow_hp;                   /* cm->allow_high_precision_mv */
+    uint8_t reference_mode;             /* SVT_MODES_SINGLE_REFERENCE .. SVT_MODES_REFERENCE_SELECT */
+    uint8_t allow_comp_inter_inter;     /* cpi->allow_comp_inter_inter */
+    /* colour and size */
+    uint8_t color_space;                /* 0 .. 6 (7, SRGB, needs profile 1) */
+    uint8_t color_range;
+    uint8_t pad0_[3];
+    int32_t width, height;              /* 1 .. 4096 (one tile column is not codable beyond), 1 .. 65536 */
+    int32_t render_width, render_height; /* 1 .. 65536 */
+    /* loop filter; the last_* fields are the stream's state in front of this frame: INPUTS (encode_loopfilter updates them in
+       place where a delta is sent; here the caller does, the struct is const) */
+    uint8_t filter_level;               /* 0 .. 63 */
+    uint8_t sharpness_level;            /* 0 .. 7 */
+    uint8_t mode_ref_delta_enabled, mode_ref_delta_update;
+    int8_t  ref_deltas[4], mode_deltas[2];            /* -63 .. 63 */
+    int8_t  last_ref_deltas[4], last_mode_deltas[2];
+    /* quantiser */
+    uint8_t base_qindex;
+    int8_t  y_dc_delta_q, uv_dc_delta_q, uv_ac_delta_q; /* -15 .. 15 */
+    uint8_t pad1_[4];
+} svt_frame_params;                     /* 64 bytes */
+/* bytes of the two headers together at most; derived from the syntax in csrc/frame_core.h */
+#define SVT_FRAME_HEADER_MAX 56
+/* out: uncompressed header (first_part_size filled in) || compressed header; the two lengths are reported.  The compressed header is
+ * built as raw bool records and coded by svt_hip_boolcode_host (framing and marker byte of eb_vp9_stop_encode included).
+ * SVT_HIP_ERR_BAD_PARAMETER, and nothing written, for: a null pointer; a width of 0 or above 4096 (eb_vp9_get_tile_n_bits then gives
+ * min_log2_tile_cols > 0); a height or a render size of 0 or above 65536; color_space 7; a delta q outside +-15; a loop-filter delta
+ * (last_* included) outside +-63; a flag above 1; frame_type, reset_frame_context, frame_context_idx, ref_dpb_index, reference_mode,
+ * filter_level or sharpness_level out of its bit width; intra_only together with show_frame on a non-key frame (the bit is not coded
+ * then); a capacity below the bytes needed (SVT_FRAME_HEADER_MAX always suffices). */
+int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes, uint32_t *compressed_bytes);
+/* the one-byte frame that shows DPB slot dpb_slot (0 .. 7): eb_vp9_pack_bitstream with show_existing_frame set */
+int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out);
+
+/* one picture of a batch.  header / trailer are HOST bytes (the two headers; up to four show-existing bytes): they travel to the device
+ * inside the descriptor upload of the call.  d_tile / d_tile_size are the bool coder's d_bytes / d_size; d_tile may have ANY alignment. */
+typedef struct svt_frame_packet {
+    const uint8_t  *d_tile;
+    const uint32_t *d_tile_size;
+    uint32_t        tile_capacity;      /* as handed to the bool coder */
+    uint8_t         header_len;         /* <= SVT_FRAME_HEADER_MAX */
+    uint8_t         trailer_len;        /* <= 4 */
+    uint8_t         header[SVT_FRAME_HEADER_MAX], trailer[4];
+    uint8_t         pad_[6];
+} svt_frame_packet;                     /* 88 bytes */
+typedef struct svt_frame_entry {
+    uint32_t offset, size;
+} svt_frame_entry;
+#define SVT_FRAME_SIZE_NONE 0xFFFFFFFFu
+#define SVT_FRAME_MAX_PICS 32
+/* Packet i = header || tile[0 .. *d_tile_size) || trailer at d_arena + d_table[i].offset, d_table[i].size bytes; offset = the sum of
+ * the sizes in front of it: dense, no padding.  d_table[n_pics] = {total bytes, pictures without a packet}, WRITTEN always, like every
+ * entry.  A picture whose *d_tile_size is SVT_BOOL_SIZE_OVERFLOW or above tile_capacity gets size = SVT_FRAME_SIZE_NONE, contributes
+ * nothing, and its offset is where it would have started.  When the total exceeds arena_capacity nothing is written at or beyond
+ * d_arena + arena_capacity and the contents are unspecified (offsets and the total saturate at 0xFFFFFFFF).
+ * Asynchronous on the context's stream, no synchronisation, one descriptor upload: behind svt_hip_boolcode_batch_device on the same
+ * context it needs no host round trip; afterwards one read of the table and one copy of `total` bytes deliver the batch.  d_arena may
+ * be device memory or pinned host memory from svt_hip_host_alloc (then no copy is needed); d_table is n_pics + 1 entries of device
+ * memory (or pinned host memory).  Refused, nothing launched: n_pics outside 1 .. SVT_FRAME_MAX_PICS, a null pointer (d_arena may
+ * be null when arena_capacity is 0, d_tile when tile_capacity is 0), header_len above SVT_FRAME_HEADER_MAX, trailer_len above 4. */
+int32_t svt_hip_frame_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_frame_packet *packets, uint8_t *d_arena, uint32_t arena_capacity,
+                                   svt_frame_entry *d_table);
+/* host form of the same text (csrc/frame_core.h), pure CPU; every pointer a host pointer */
+int32_t svt_hip_frame_assemble_host(int32_t n_pics, const svt_frame_packet *packets, uint8_t *arena, uint32_t arena_capacity, svt_frame_entry *table);
+/* the assembly kernel's constants: workgroups per picture and bytes they move in one pass of the grid-stride loop */
+void svt_hip_frame_geometry(int32_t *workgroups_per_picture, int32_t *bytes_per_pass);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* IVF container (host only): what the reference's sample application wraps the encoder's packets in   */

@@ -212,6 +212,32 @@ class MvrefsPicture(C.Structure):
                 ("ref_mask", C.c_uint8), ("restrict_ref_mvs", C.c_uint8), ("ref_frame_sign_bias", C.c_uint8 * 4), ("pad_", C.c_uint8 * 2)]
 
 
+# frame stage (svt_frame_params / svt_frame_packet / svt_frame_entry of include/svtvp9_hip.h)
+FRAME_HEADER_MAX = 56
+FRAME_SIZE_NONE = 0xFFFFFFFF
+FRAME_MAX_PICS = 32
+FRAME_ENTRY_DTYPE = np.dtype([("offset", "<u4"), ("size", "<u4")])
+
+
+class FrameParams(C.Structure):
+    _fields_ = [("frame_type", C.c_uint8), ("show_frame", C.c_uint8), ("error_resilient_mode", C.c_uint8), ("intra_only", C.c_uint8),
+                ("reset_frame_context", C.c_uint8), ("refresh_frame_context", C.c_uint8), ("frame_parallel_decoding_mode", C.c_uint8),
+                ("frame_context_idx", C.c_uint8), ("refresh_frame_mask", C.c_uint8), ("ref_dpb_index", C.c_uint8 * 3), ("ref_frame_sign_bias", C.c_uint8 * 4),
+                ("allow_hp", C.c_uint8), ("reference_mode", C.c_uint8), ("allow_comp_inter_inter", C.c_uint8), ("color_space", C.c_uint8),
+                ("color_range", C.c_uint8), ("pad0_", C.c_uint8 * 3), ("width", C.c_int32), ("height", C.c_int32), ("render_width", C.c_int32),
+                ("render_height", C.c_int32), ("filter_level", C.c_uint8), ("sharpness_level", C.c_uint8), ("mode_ref_delta_enabled", C.c_uint8),
+                ("mode_ref_delta_update", C.c_uint8), ("ref_deltas", C.c_int8 * 4), ("mode_deltas", C.c_int8 * 2), ("last_ref_deltas", C.c_int8 * 4),
+                ("last_mode_deltas", C.c_int8 * 2), ("base_qindex", C.c_uint8), ("y_dc_delta_q", C.c_int8), ("uv_dc_delta_q", C.c_int8),
+                ("uv_ac_delta_q", C.c_int8), ("pad1_", C.c_uint8 * 4)]
+
+
+class FramePacket(C.Structure):
+    _fields_ = [("d_tile", C.c_void_p), ("d_tile_size", C.c_void_p), ("tile_capacity", C.c_uint32), ("header_len", C.c_uint8), ("trailer_len", C.c_uint8),
+                ("header", C.c_uint8 * FRAME_HEADER_MAX), ("trailer", C.c_uint8 * 4), ("pad_", C.c_uint8 * 6)]
+
+
+assert C.sizeof(FrameParams) == 64 and C.sizeof(FramePacket) == 88 and FRAME_ENTRY_DTYPE.itemsize == 8
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -247,6 +273,7 @@ EXPORTS = [
     "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
     "svt_hip_modes_inter_set_tables", "svt_hip_modes_inter_batch_device", "svt_hip_modes_inter_picture", "svt_hip_modes_inter_bools_capacity",
     "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
+    "svt_hip_frame_header_host", "svt_hip_frame_show_existing_host", "svt_hip_frame_batch_device", "svt_hip_frame_assemble_host", "svt_hip_frame_geometry",
 ]
 
 _lib = None
@@ -288,6 +315,11 @@ def load():
         _u32 = C.c_uint32
         _lib.svt_hip_boolcode_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p, _u32, C.POINTER(_u32)]
         _lib.svt_hip_boolcode.argtypes = [C.c_void_p] + _lib.svt_hip_boolcode_host.argtypes[1:]
+        _lib.svt_hip_frame_header_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.POINTER(_u32), C.POINTER(_u32)]
+        _lib.svt_hip_frame_show_existing_host.argtypes = [C.c_int32, C.c_void_p]
+        _lib.svt_hip_frame_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
+        _lib.svt_hip_frame_assemble_host.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
+        _lib.svt_hip_frame_geometry.restype = None
         _lib.svt_hip_encdec_work_destroy.restype = None
         _lib.svt_hip_host_free.restype = None
         _lib.svt_hip_encdec_work_set_stage_hook.restype = None
