@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include "svt_ctx.h"
 #include "boolcode_core.h"
+#include "wave_ops.h"
 
 #define BC_K 256          /* bools per chunk */
 #define BC_TILE 32        /* chunks per LDS tile of the chain kernel */
@@ -60,18 +61,14 @@ struct bc_batch_dev {
 /* exclusive prefix of v over the 256 lanes of the workgroup, *total = the sum; s_w: 4 entries of LDS, free again on return */
 template <typename T> __device__ __forceinline__ T block_excl_scan(T v, T *s_w, T *total) {
     const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
-    T         incl = v;
-    _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_w[wv] = incl;
+    const T   ex = wave_excl_prefix(v, lane);
+    if (lane == 63) s_w[wv] = ex + v;
     __syncthreads();
     T base = 0;
     for (int i = 0; i < wv; i++) base += s_w[i];
     *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
     __syncthreads();
-    return base + incl - v;
+    return base + ex;
 }
 
 __global__ __launch_bounds__(256) void svt_bc_segscan_kernel(const bc_batch_dev *__restrict__ B) {

@@ -24,6 +24,7 @@
 #include <string.h>
 #include "svt_ctx.h"
 #include "encdec_core.h"
+#include "wave_ops.h"
 
 #define ED_MAX_PICS 32
 #define ED_MAX_SETS 8 /* reconstruction base pointers a transform launch can address (svt_tq_block.pad_[0] bits 4-6) */
@@ -64,19 +65,6 @@ struct ed_batch_dev {
     uint32_t   lambda;
     int32_t    filter_level;
 };
-
-__device__ __forceinline__ int wave_sum(int v) {
-    _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_excl_prefix(int v, int lane) {
-    int incl = v;
-    _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    return incl - v;
-}
 
 /* one wave per (picture, SB), one lane per 8x8 unit: per-SB number of transform blocks of each size; also clears the unit's
  * "has coefficients" scratch byte for the skip pass */

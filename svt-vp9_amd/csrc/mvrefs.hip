@@ -12,13 +12,14 @@
  *                           only the mode of a unit comes from elsewhere, the origin of its leaf, which may lie outside the window.
  *                           The lanes then run the walk from LDS alone and write their unit's records; the wave leaves its two sums
  *                           (contradicting leaves, inter leaves), or SVT_MODES_BAD_GRID, in the context's scratch
- *   svt_mvr_status_kernel   one workgroup per picture: the sums of the SBs -> d_status, in the shape of svt_mii_scan_kernel
+ *   svt_mvr_status_kernel   one workgroup per picture: the sums of the SBs -> d_status, in the shape of syn_scan_kernel (syntax_stage.h)
  * 1 452 bytes of LDS per wave: the 160 KB of a CU hold far more waves than its SIMDs take.  No atomics, and workgroups do not talk to
  * each other: the two passes are separate launches in stream order.
  */
 #include <hip/hip_runtime.h>
 #include "svt_ctx.h"
 #include "mvrefs_core.h"
+#include "wave_ops.h"
 
 #define MVR_MAX_PICS 32
 #define MVR_SCRATCH_SLOT 54
@@ -36,11 +37,6 @@ struct mvr_batch_dev {
     svt_tok_geom g;
     int32_t      n_sb, sb_cols;
 };
-
-__device__ __forceinline__ int mvr_wave_sum(int v) {
-    _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void svt_mvr_derive_kernel(const mvr_batch_dev *__restrict__ B) {
     __shared__ uint32_t s_win[SVT_MVR_WIN_WORDS];
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(64) void svt_mvr_derive_kernel(const mvr_batch_dev 
     const int  r = sb_r + ur, c = sb_c + uc;
     const bool in = r < g.mi_rows && c < g.mi_cols;
     const bool bad = in && svt_mvr_check(&P.v, &g, r, c);
-    const int  any_bad = mvr_wave_sum(bad ? 1 : 0);
+    const int  any_bad = wave_sum(bad ? 1 : 0);
     __syncthreads();
     int contradicts = 0, inter_leaf = 0;
     /* (an SB with a record the stage does not take is not analysed: its fields may be anything) */
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(64) void svt_mvr_derive_kernel(const mvr_batch_dev 
             }
         }
     }
-    const int n_contra = mvr_wave_sum(contradicts), n_inter = mvr_wave_sum(inter_leaf);
+    const int n_contra = wave_sum(contradicts), n_inter = wave_sum(inter_leaf);
     if (lane == 0) {
         P.part[2 * sb] = any_bad ? SVT_MODES_BAD_GRID : (uint32_t)n_contra;
         P.part[2 * sb + 1] = any_bad ? SVT_MODES_BAD_GRID : (uint32_t)n_inter;

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "svt_ctx.h"
 #include "tokenize_core.h"
+#include "wave_ops.h"
 
 #define TOK_MAX_PICS 32
 #define TOK_SB_RUN 8          /* SBs per workgroup of the emit kernel: 8 x 6144 tokens at most (< 65536) */
@@ -43,19 +44,6 @@ struct tok_batch_dev {
     svt_tok_geom g;
     int32_t      n_sb, sb_cols;
 };
-
-__device__ __forceinline__ int wave_sum(int v) {
-    _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_excl_prefix(int v, int lane) {
-    int incl = v;
-    _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    return incl - v;
-}
 
 /* the (at most) six transform blocks that start in the 8x8 unit `lane` (z-order) of an SB: four luma 4x4 units, one chroma unit per
  * plane.  info[i] = packed description or 0xFFFFFFFF, cnt[i] = tokens */

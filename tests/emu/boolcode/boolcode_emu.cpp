@@ -1,35 +1,13 @@
 /*
  * boolcode_emu.cpp -- csrc/boolcode.hip itself (kernels and entry points, included below) on the CPU through the stand-in runtime of
- * hip/hip_runtime.h: random token / bool streams with and without segment lists (cuts behind EOB tokens, raw runs, empty segments)
+ * tests/emu/hip/hip_runtime.h: random token / bool streams with and without segment lists (cuts behind EOB tokens, raw runs, empty segments)
  * through svt_hip_boolcode, compared byte for byte with svt_hip_boolcode_host.  argv[1]: a file holding one svt_bool_tables.
  * Streams reach past one tile of the chain kernel (8 192 bools) and past one tile of the carry kernel (256 words); the last two (tokens
  * and bools under a segment list, then raw bools alone) have more than 256 x 1024 items: a second pass of the tile scan with its carried sum.
  */
 #include "boolcode.hip"
-#include <stdio.h>
+#include "emu_harness.h"
 #include <random>
-thread_local dim3 threadIdx, blockIdx, blockDim;
-pthread_barrier_t *g_bar;
-unsigned long long g_shfl[1024];
-void emu_launch(dim3 grid, dim3 block, std::function<void()> body) {
-    pthread_barrier_t bar; pthread_barrier_init(&bar, nullptr, block.x); g_bar = &bar;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < block.x; t++) th.emplace_back([=] {
-        blockDim = block; threadIdx = dim3(t);
-        for (unsigned by = 0; by < grid.y; by++) for (unsigned bx = 0; bx < grid.x; bx++) { blockIdx = dim3(bx, by); body(); pthread_barrier_wait(g_bar); }
-    });
-    for (auto &t : th) t.join();
-    pthread_barrier_destroy(&bar);
-}
-int32_t svt_set_error(int32_t c, const char *m) { fprintf(stderr, "error %d %s\n", c, m); return c; }
-int32_t svt_set_hip_error(hipError_t e, const char *f, int l) { return -1; }
-static char stage_h[65536], stage_d[65536];
-int svt_ctx_stage(svt_hip_ctx *, size_t n, void **h, void **d) { *h = stage_h; *d = stage_d; return n > sizeof stage_h; }
-void svt_ctx_stage_commit(svt_hip_ctx *) {}
-void *svt_ctx_slot(svt_hip_ctx *c, int s, size_t bytes) {
-    if (bytes > c->slot_bytes[s]) { free(c->slot[s]); hipMalloc(&c->slot[s], bytes); c->slot_bytes[s] = bytes; }
-    return c->slot[s];
-}
 int main(int argc, char **argv) {
     static svt_hip_ctx ctx;
     svt_bool_tables tab;

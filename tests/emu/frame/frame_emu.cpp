@@ -1,6 +1,6 @@
 /*
  * frame_emu.cpp -- csrc/frame.hip itself (kernel and entry point, included below) on the CPU through the stand-in runtime of
- * hip/hip_runtime.h: the packet batches tests/frame_model.py makes (argv[1], written by tests/test_frame.py) through
+ * tests/emu/hip/hip_runtime.h: the packet batches tests/frame_model.py makes (argv[1], written by tests/test_frame.py) through
  * svt_hip_frame_batch_device, compared byte for byte -- arena, guards, table -- with svt_hip_frame_assemble_host.  Every tile lives in an
  * allocation of its own that is exactly the 16-byte blocks holding its bytes (its start at the batch's offset mod 16), so a build with
  * -fsanitize=address reports a load from a block that holds no source byte; the arena's guards show a store outside it.
@@ -9,24 +9,7 @@
  *       uint32 size, uint32 capacity, int32 header_len, trailer_len, 56 header bytes, 4 trailer bytes
  */
 #include "frame.hip"
-#include <stdio.h>
-thread_local dim3 threadIdx, blockIdx, blockDim;
-pthread_barrier_t *g_bar;
-void emu_launch(dim3 grid, dim3 block, std::function<void()> body) {
-    pthread_barrier_t bar; pthread_barrier_init(&bar, nullptr, block.x); g_bar = &bar;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < block.x; t++) th.emplace_back([=] {
-        blockDim = block; threadIdx = dim3(t);
-        for (unsigned by = 0; by < grid.y; by++) for (unsigned bx = 0; bx < grid.x; bx++) { blockIdx = dim3(bx, by); body(); pthread_barrier_wait(g_bar); }
-    });
-    for (auto &t : th) t.join();
-    pthread_barrier_destroy(&bar);
-}
-int32_t svt_set_error(int32_t c, const char *m) { fprintf(stderr, "error %d %s\n", c, m); return c; }
-int32_t svt_set_hip_error(hipError_t e, const char *f, int l) { return -1; }
-static char stage_h[65536], stage_d[65536];
-int svt_ctx_stage(svt_hip_ctx *, size_t n, void **h, void **d) { *h = stage_h; *d = stage_d; return n > sizeof stage_h; }
-void svt_ctx_stage_commit(svt_hip_ctx *) {}
+#include "emu_harness.h"
 
 #define GUARD 64
 static bool rd(FILE *f, void *p, size_t n) { return fread(p, 1, n, f) == n; }

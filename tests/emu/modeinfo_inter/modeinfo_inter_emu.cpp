@@ -1,38 +1,13 @@
 /*
  * modeinfo_inter_emu.cpp -- csrc/modeinfo_inter.hip itself (kernels and entry points, included below) on the CPU through the stand-in
- * runtime of hip/hip_runtime.h, compared with svt_hip_modes_inter_picture: bool records up to the capacity, the guard words behind
+ * runtime of tests/emu/hip/hip_runtime.h, compared with svt_hip_modes_inter_picture: bool records up to the capacity, the guard words behind
  * them, every segment record, the bool total.  argv[1]: a file holding one svt_modes_inter_tables, then int32 n_groups; per group int32
  * width, height, mi_stride, n_pics, then per picture int32 capacity, 9 bytes of frame parameters (reference_mode, allow_hp,
  * comp_fixed_ref, comp_var_ref[2], ref_frame_sign_bias[4]), the three grids (mi_rows x mi_stride records each: svt_lf_mode_info,
  * svt_mc_mode_info, svt_mi_inter_ext), the eob map (uint16), the tokeniser's offsets (uint32).  A group is one batch call.
  */
 #include "modeinfo_inter.hip"
-#include <stdio.h>
-thread_local dim3 threadIdx, blockIdx, blockDim;
-pthread_barrier_t *g_bar, *g_wave_bar;
-long long g_shfl[1024];
-void emu_launch(dim3 grid, dim3 block, std::function<void()> body) {
-    pthread_barrier_t bar, wave[16];
-    pthread_barrier_init(&bar, nullptr, block.x);
-    for (unsigned w = 0; w < (block.x + 63) / 64; w++) pthread_barrier_init(&wave[w], nullptr, block.x - 64 * w < 64 ? block.x - 64 * w : 64);
-    g_bar = &bar; g_wave_bar = wave;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < block.x; t++) th.emplace_back([=] {
-        blockDim = block; threadIdx = dim3(t);
-        for (unsigned by = 0; by < grid.y; by++) for (unsigned bx = 0; bx < grid.x; bx++) { blockIdx = dim3(bx, by); body(); pthread_barrier_wait(g_bar); }
-    });
-    for (auto &t : th) t.join();
-    pthread_barrier_destroy(&bar);
-}
-int32_t svt_set_error(int32_t c, const char *m) { fprintf(stderr, "error %d %s\n", c, m); return c; }
-int32_t svt_set_hip_error(hipError_t e, const char *f, int l) { return -1; }
-static char stage_h[65536], stage_d[65536];
-int svt_ctx_stage(svt_hip_ctx *, size_t n, void **h, void **d) { *h = stage_h; *d = stage_d; return n > sizeof stage_h; }
-void svt_ctx_stage_commit(svt_hip_ctx *) {}
-void *svt_ctx_slot(svt_hip_ctx *c, int s, size_t bytes) {
-    if (bytes > c->slot_bytes[s]) { free(c->slot[s]); hipMalloc(&c->slot[s], bytes); c->slot_bytes[s] = bytes; }
-    return c->slot[s];
-}
+#include "emu_harness.h"
 struct pic_bufs {
     std::vector<svt_lf_mode_info> mi;
     std::vector<svt_mc_mode_info> mc;

@@ -1,38 +1,13 @@
 /*
  * mvrefs_emu.cpp -- csrc/mvrefs.hip itself (kernels and entry point, included below) on the CPU through the stand-in runtime of
- * hip/hip_runtime.h, compared with svt_hip_mvrefs_picture: every byte of d_ext_out and d_cand with the guard bytes behind them, and the
+ * tests/emu/hip/hip_runtime.h, compared with svt_hip_mvrefs_picture: every byte of d_ext_out and d_cand with the guard bytes behind them, and the
  * status words (the two buffers are left out of the comparison for a grid the stage does not take: their contents are unspecified).
  * argv[1]: a file holding int32 n_groups; per group int32 width, height, mi_stride, n_pics, then per picture 8 bytes (ref_mask,
  * restrict_ref_mvs, ref_frame_sign_bias[4], d_ext_out wanted, d_cand wanted) and the three grids (mi_rows x mi_stride records each:
  * svt_lf_mode_info, svt_mc_mode_info, svt_mi_inter_ext).  A group is one batch call.
  */
 #include "mvrefs.hip"
-#include <stdio.h>
-thread_local dim3 threadIdx, blockIdx, blockDim;
-pthread_barrier_t *g_bar, *g_wave_bar;
-long long g_shfl[1024];
-void emu_launch(dim3 grid, dim3 block, std::function<void()> body) {
-    pthread_barrier_t bar, wave[16];
-    pthread_barrier_init(&bar, nullptr, block.x);
-    for (unsigned w = 0; w < (block.x + 63) / 64; w++) pthread_barrier_init(&wave[w], nullptr, block.x - 64 * w < 64 ? block.x - 64 * w : 64);
-    g_bar = &bar; g_wave_bar = wave;
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < block.x; t++) th.emplace_back([=] {
-        blockDim = block; threadIdx = dim3(t);
-        for (unsigned by = 0; by < grid.y; by++) for (unsigned bx = 0; bx < grid.x; bx++) { blockIdx = dim3(bx, by); body(); pthread_barrier_wait(g_bar); }
-    });
-    for (auto &t : th) t.join();
-    pthread_barrier_destroy(&bar);
-}
-int32_t svt_set_error(int32_t c, const char *m) { fprintf(stderr, "error %d %s\n", c, m); return c; }
-int32_t svt_set_hip_error(hipError_t e, const char *f, int l) { return -1; }
-static char stage_h[65536], stage_d[65536];
-int svt_ctx_stage(svt_hip_ctx *, size_t n, void **h, void **d) { *h = stage_h; *d = stage_d; return n > sizeof stage_h; }
-void svt_ctx_stage_commit(svt_hip_ctx *) {}
-void *svt_ctx_slot(svt_hip_ctx *c, int s, size_t bytes) {
-    if (bytes > c->slot_bytes[s]) { free(c->slot[s]); hipMalloc(&c->slot[s], bytes); c->slot_bytes[s] = bytes; }
-    return c->slot[s];
-}
+#include "emu_harness.h"
 #define GUARD 64
 struct pic_bufs {
     std::vector<svt_lf_mode_info> mi;

@@ -1,4 +1,4 @@
-"""CPU: the bool coder's kernels themselves (csrc/boolcode.hip compiled as plain C++ against tests/emu/boolcode/hip/hip_runtime.h, one
+"""CPU: the bool coder's kernels themselves (csrc/boolcode.hip compiled as plain C++ against tests/emu/hip/hip_runtime.h, one
 thread per lane) against svt_hip_boolcode_host on random streams with and without segment lists -- the scans, the expansion, the chunk
 maps, the chain, the word sums and the carry scan as the device runs them, without a device."""
 import os
@@ -13,7 +13,7 @@ def test_kernel_text_on_the_cpu_equals_the_host_form():
     emu, src = os.path.join(T.ROOT, "tests", "emu", "boolcode"), os.path.join(T.ROOT, "svt-vp9_amd")
     with tempfile.TemporaryDirectory() as td:
         exe, tab = os.path.join(td, "boolcode_emu"), os.path.join(td, "tables.bin")
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{emu}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "boolcode_emu.cpp"),
+        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{os.path.dirname(emu)}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "boolcode_emu.cpp"),
                                "-x", "c", os.path.join(src, "host", "boolcode_host.c"), "-lpthread", "-o", exe])
         with open(tab, "wb") as f:
             f.write(BM.tables()[1].tobytes())

@@ -2,7 +2,7 @@
 every case from svt_hip_frame_header_host and from the independent model tests/frame_model.py, the show-existing bytes, whole frames,
 refusals, struct sizes, SVT_FRAME_HEADER_MAX over a seeded sweep; the packet layout (svt_hip_frame_assemble_host) against a numpy
 concatenation with the overflow and short-arena rules; and the assembly kernel's own text on the CPU (csrc/frame.hip compiled as plain C++
-against tests/emu/frame/hip/hip_runtime.h, one thread per lane) against the host form, once more under AddressSanitizer and UBSan as a
+against tests/emu/hip/hip_runtime.h, one thread per lane) against the host form, once more under AddressSanitizer and UBSan as a
 stand-alone program where the host compiler links one."""
 import ctypes as C
 import os
@@ -268,7 +268,7 @@ def build_emu(td, sanitize):
     emu, src = os.path.join(T.ROOT, "tests", "emu", "frame"), os.path.join(T.ROOT, "svt-vp9_amd")
     exe = os.path.join(td, "frame_emu_san" if sanitize else "frame_emu")
     cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-DFR_WGS={EMU_WGS}"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []) + \
-          [f"-I{emu}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "frame_emu.cpp"), "-x", "c", os.path.join(src, "host", "frame_host.c"),
+          [f"-I{os.path.dirname(emu)}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "frame_emu.cpp"), "-x", "c", os.path.join(src, "host", "frame_host.c"),
            os.path.join(src, "host", "boolcode_host.c"), "-lpthread", "-o", exe]
     return exe if subprocess.run(cmd, capture_output=True).returncode == 0 else None
 

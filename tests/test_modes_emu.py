@@ -1,4 +1,4 @@
-"""CPU: the mode-info stage's kernels themselves (csrc/modeinfo.hip compiled as plain C++ against tests/emu/modeinfo/hip/hip_runtime.h,
+"""CPU: the mode-info stage's kernels themselves (csrc/modeinfo.hip compiled as plain C++ against tests/emu/hip/hip_runtime.h,
 one thread per lane) against svt_hip_modes_kf_picture on the fixture pictures, singly and as batches of one geometry, with full, short and
 no bool capacity, on the malformed grids, on the unit with the most bools and on 1080x1080 pictures of 289 SBs -- the count, the scan, the LDS assembly, the dword stores and the segment slots as the
 device runs them, without a device."""
@@ -49,7 +49,7 @@ def test_kernel_text_on_the_cpu_equals_the_host_form():
     emu, src = os.path.join(T.ROOT, "tests", "emu", "modeinfo"), os.path.join(T.ROOT, "svt-vp9_amd")
     with tempfile.TemporaryDirectory() as td:
         exe, req = os.path.join(td, "modeinfo_emu"), os.path.join(td, "req.bin")
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{emu}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "modeinfo_emu.cpp"),
+        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{os.path.dirname(emu)}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "modeinfo_emu.cpp"),
                                "-x", "c", os.path.join(src, "host", "modeinfo_host.c"), "-lpthread", "-o", exe])
         with open(req, "wb") as f:
             f.write(MM.tables()[1].tobytes())

@@ -1,4 +1,4 @@
-"""CPU: the MV-reference stage's kernels themselves (csrc/mvrefs.hip compiled as plain C++ against tests/emu/mvrefs/hip/hip_runtime.h,
+"""CPU: the MV-reference stage's kernels themselves (csrc/mvrefs.hip compiled as plain C++ against tests/emu/hip/hip_runtime.h,
 one thread per lane) against svt_hip_mvrefs_picture: every fixture picture singly, batches of one geometry whose pictures differ in
 restrict flag, sign biases and ref_mask, optional outputs left out, the malformed grids, wider grids and a 1080x1080 picture of 289 SBs
 -- the window staging, the walk from the window, the record stores and the two-pass status as the device runs them, without a device.
@@ -20,7 +20,7 @@ B = T.B
 def build(td):
     emu, src = os.path.join(T.ROOT, "tests", "emu", "mvrefs"), os.path.join(T.ROOT, "svt-vp9_amd")
     exe = os.path.join(td, "mvrefs_emu")
-    cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{emu}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "mvrefs_emu.cpp"),
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-w", f"-I{os.path.dirname(emu)}", f"-I{os.path.join(src, 'csrc')}", os.path.join(emu, "mvrefs_emu.cpp"),
            "-x", "c", os.path.join(src, "host", "mvrefs_host.c"), "-lpthread", "-o", exe]
     sanitized = subprocess.run(cmd[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] + cmd[1:], capture_output=True).returncode == 0
     if not sanitized:
