@@ -363,4 +363,27 @@ SVT_HD void svt_md_intra_search_unit(const svt_ois_block *ois, int r, int c, int
     }
 }
 
+/* ------------------------------------------------------------------------------------------------------------------------ */
+/* the intra pass's wavefront (csrc/intra_kernel.hip): ticket -> 16x16 cell                                                   */
+/* ------------------------------------------------------------------------------------------------------------------------ */
+/* The n-th cell of a c_rows x c_cols grid in anti-diagonal order (diagonal d = row + col, rows ascending inside a diagonal): cells before
+ * diagonal d in closed form (growing part d (d + 1) / 2, then full diagonals of m = min(rows, cols) cells, then the shrinking tail), d by
+ * bisection.  The left and the above neighbour of a cell lie on the diagonal before its own, so they hold smaller n: a worker of the intra
+ * kernel only ever waits for tickets smaller than its own (tests/test_intra_wavefront.py checks exactly that, on the host). */
+SVT_HD int svt_intra_cells_before_diagonal(int d, int m, int M) { /* cells on diagonals 0 .. d-1 */
+    const int a = d < m ? d : m;                        /* growing diagonals 0 .. a-1: 1 .. a cells */
+    int       t = a * (a + 1) / 2;
+    if (d > m) { const int fl = (d < M ? d : M) - m; t += fl * m; }          /* diagonals m .. min(d, M)-1: m cells each */
+    if (d > M) { const int k = d - M; t += k * m - k * (k + 1) / 2; }         /* diagonals M .. d-1: m-1, m-2, .. cells */
+    return t;
+}
+SVT_HD void svt_intra_cell_of_ticket(int n, int c_rows, int c_cols, int *cr, int *cc) {
+    const int m = c_rows < c_cols ? c_rows : c_cols, M = c_rows < c_cols ? c_cols : c_rows;
+    int lo = 0, hi = c_rows + c_cols - 1; /* largest d with count(d) <= n */
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (svt_intra_cells_before_diagonal(mid, m, M) <= n) lo = mid; else hi = mid; }
+    const int d = lo, r_lo = d - (c_cols - 1) > 0 ? d - (c_cols - 1) : 0;
+    *cr = r_lo + (n - svt_intra_cells_before_diagonal(d, m, M));
+    *cc = d - *cr;
+}
+
 #endif /* SVT_ENCDEC_CORE_H */

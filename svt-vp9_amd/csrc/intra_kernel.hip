@@ -189,7 +189,6 @@ __global__ __launch_bounds__(64 * INTRA_W) __attribute__((amdgpu_waves_per_eu(IN
      * coded by the ticket of its TOP-RIGHT cell -- every cell it depends on then lies on an earlier diagonal, so a worker still only ever
      * waits for smaller tickets -- which sets all four flags; the tickets of its other three cells have nothing to do. */
     const int lane = (int)__lane_id(), c_cols = (P.width + 15) >> 4, c_rows = (P.height + 15) >> 4, n_cell = c_cols * c_rows;
-    const int n_diag = c_rows + c_cols - 1;
     /* a wave on a chain of dependent blocks, beside kernels that fill the SIMDs: it issues rarely, so letting it go first costs
      * the others next to nothing and keeps the chain at the speed it has alone */
     __builtin_amdgcn_s_setprio(3);
@@ -215,20 +214,9 @@ __global__ __launch_bounds__(64 * INTRA_W) __attribute__((amdgpu_waves_per_eu(IN
     if (ticket >= 3 * n_cell) break;
 #endif
     const int plane = ticket % 3;
-    /* the n-th cell in anti-diagonal order (diagonal d = row + col, rows ascending inside a diagonal): cells before diagonal d in closed form
-     * (growing part d (d + 1) / 2, then full diagonals of m = min(rows, cols) cells, then the shrinking tail), d by bisection */
-    const int n = ticket / 3, m = c_rows < c_cols ? c_rows : c_cols, M = c_rows < c_cols ? c_cols : c_rows;
-    int lo = 0, hi = n_diag; /* largest d with count(d) <= n */
-    auto count = [&](int d) -> int { /* cells on diagonals 0 .. d-1 */
-        const int a = d < m ? d : m;                        /* growing diagonals 0 .. a-1: 1 .. a cells */
-        int       t = a * (a + 1) / 2;
-        if (d > m) { const int fl = (d < M ? d : M) - m; t += fl * m; }          /* diagonals m .. min(d, M)-1: m cells each */
-        if (d > M) { const int k = d - M; t += k * m - k * (k + 1) / 2; }         /* diagonals M .. d-1: m-1, m-2, .. cells */
-        return t;
-    };
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (count(mid) <= n) lo = mid; else hi = mid; }
-    const int d = lo, r_lo = d - (c_cols - 1) > 0 ? d - (c_cols - 1) : 0;
-    const int cr = r_lo + (n - count(d)), cc = d - cr;
+    /* the n-th cell in anti-diagonal order (encdec_core.h: the same text runs on the host, where the order is checked for every grid shape) */
+    int cr, cc;
+    svt_intra_cell_of_ticket(ticket / 3, c_rows, c_cols, &cr, &cc);
     const int cell = cr * c_cols + cc;
     int32_t  *done = P.sync + 2 + plane * n_cell;
     /* what the cell belongs to: the unit at the origin of its 2 x 2 cell group decides (a 32x32 block starts there or nowhere in the group), so

@@ -3,6 +3,7 @@ reconstruction over the blocks of the mode-info grid -> skip flags -> loop-filte
 each stage the oracle's (oracle/*.c), composed on the host exactly as svt_hip_encdec_batch_device composes the kernels.
 Used by tests/test_gpu_encdec.py and tests/test_enc_shim.py to check the device chain and the encoder shim's reconstruction."""
 import ctypes as C
+import os
 import time
 
 import numpy as np
@@ -281,6 +282,133 @@ def ref_intra_picture(src, lf_mi, q_index):
     out["eob_map"] = np.frombuffer(raw, np.uint16, ne, o).copy()
     assert o + 2 * ne == len(raw)
     return out
+
+
+# The cases of tests/golden/intra_reference.npz (written by tests/gen_golden_intra.py from the reference's own functions):
+# (name, W, H, seed, q_index, content kind); every grid is gen_intra_grid(seed, W, H, sizes=(4, 8, 16, 32)).
+#   thin_*: pictures of fewer than four 16x16 cells in one direction or both (cell grids 1x1 .. 7x2): the three branches of the wavefront's
+#           ticket -> cell mapping at min(rows, cols) of 1, 2, 3, 2 x 2 cell groups cut by the picture edge, mi_rows == 1, chroma planes four
+#           samples wide, launches of fewer workers than a workgroup holds;
+#   q*_*:   the ends of the q range on natural and on 0 / 255 content: the largest coefficients the quantiser gives (q 0, q 1) and the
+#           smallest (q 254, q 255).  Their seeds give grids that hold all four block sizes.
+INTRA_GOLDEN_SIZES = (4, 8, 16, 32)
+INTRA_GOLDEN_CASES = tuple(
+    [(f"thin_{W}x{H}", W, H, 40 + k, 100, "nat") for k, (W, H) in enumerate(((8, 8), (16, 8), (8, 16), (8, 72), (72, 8), (16, 16), (24, 40), (40, 24), (32, 32), (48, 32),
+                                                                             (32, 104)))] +
+    [(f"q{q}_{kind}", 64, 40, seed, q, kind) for q, seeds in ((0, (1, 2, 5, 1)), (255, (10, 11, 2, 5))) for kind, seed in zip(("nat", "blocks", "noise", "flat"), seeds)] +
+    [("q1_blocks", 64, 40, 10, 1, "blocks"), ("q254_blocks", 64, 40, 1, 254, "blocks")])
+INTRA_GOLDEN = os.path.join(T.ROOT, "tests", "golden", "intra_reference.npz")
+INTRA_GOLDEN_KEYS = ("pred", "rec", "qcoeff", "dqcoeff", "eob_map")
+
+
+def intra_content(W, H, seed, kind):
+    """(Y, Cb, Cr) tight planes.  nat: gen_yuv's picture; blocks: 4x4 blocks of 0 or 255 with 15 % of the samples inverted; noise: every
+    sample 0 or 255; flat: one value (never 128, so that DC_128 does not predict it).  Chroma is derived from luma, Cr inverted: the chroma
+    planes clamp from both sides where luma does."""
+    rng = np.random.default_rng(1000 + seed)
+    if kind == "nat":
+        y, u, _ = T.gen_yuv(W, H, seed)
+        return y, u, (255 - y[1::2, ::2] // 2).astype(np.uint8)
+    if kind == "blocks":
+        y = np.kron(rng.integers(0, 2, ((H + 3) // 4, (W + 3) // 4)), np.ones((4, 4), np.int64))[:H, :W] * 255
+        y = np.where(rng.random((H, W)) < 0.15, 255 - y, y).astype(np.uint8)
+    elif kind == "noise":
+        y = (rng.integers(0, 2, (H, W)) * 255).astype(np.uint8)
+    elif kind == "flat":
+        y = np.full((H, W), (60, 200, 17, 250)[seed // 4 % 4], np.uint8)
+    else:
+        raise ValueError(kind)
+    return y, y[::2, ::2].copy(), (255 - y[1::2, ::2]).astype(np.uint8)
+
+
+def intra_golden_inputs(case):
+    """(src, mi) of one INTRA_GOLDEN_CASES entry"""
+    _, W, H, seed, _, kind = case
+    return intra_content(W, H, seed, kind), gen_intra_grid(seed, W, H, sizes=INTRA_GOLDEN_SIZES)
+
+
+def intra_flat(out):
+    """the outputs of oracle_intra_picture / ref_intra_picture as the fixture stores them: tight planes one after the other"""
+    rec = out["rec"].interior() if isinstance(out["rec"], RefPic) else out["rec"]
+    return dict(pred=np.concatenate([p.ravel() for p in out["pred"]]), rec=np.concatenate([p.ravel() for p in rec]),
+                qcoeff=out["qcoeff"], dqcoeff=out["dqcoeff"], eob_map=out["eob_map"])
+
+
+_intra_golden = None
+
+
+def intra_golden():
+    """{name: {pred, rec, qcoeff, dqcoeff, eob_map, src, mi}}: what the reference made of every case, and the source planes and the
+    grid (as bytes) it was given (loaded once, read-only)"""
+    global _intra_golden
+    if _intra_golden is None:
+        z = np.load(INTRA_GOLDEN)
+        _intra_golden = {n: {k: z[f"{k}|{n}"] for k in INTRA_GOLDEN_KEYS + ("src", "mi")} for n in z["names"].tolist()}
+        for d in _intra_golden.values():
+            for a in d.values():
+                a.setflags(write=False)
+    return _intra_golden
+
+
+def intra_blocks(lf_mi, W, H):
+    """(plane, x0, y0, n, mode) of every block an intra grid codes, luma then the two chroma planes"""
+    out = []
+    for ur in range(H // 8):
+        for uc in range(W // 8):
+            m = lf_mi[ur, uc]
+            st = int(m["sb_type"])
+            n8 = {0: 1, 3: 1, 6: 2, 9: 4}[st]
+            if ur % n8 or uc % n8:
+                continue
+            if st == 0:
+                md = int(m["pad"][1]) | int(m["pad"][0]) << 8
+                out += [(0, uc * 8 + 4 * (k & 1), ur * 8 + 4 * (k >> 1), 4, (md >> (4 * k)) & 15) for k in range(4)]
+            else:
+                out.append((0, uc * 8, ur * 8, 8 * n8, int(m["pad"][1])))
+            out += [(p, uc * 4, ur * 4, 4 * n8, int(m["pad"][2])) for p in (1, 2)]
+    return out
+
+
+def intra_planes(flat, W, H):
+    """tight planes (Y, Cb, Cr) of a flat fixture array"""
+    ny, nc = W * H, W * H // 4
+    return flat[:ny].reshape(H, W), flat[ny:ny + nc].reshape(H // 2, W // 2), flat[ny + nc:].reshape(H // 2, W // 2)
+
+
+def tm_blocks_clamped_both_ways(rec, lf_mi, W, H):
+    """number of TM blocks (with a left and an above neighbour) whose unclamped prediction left + above - corner, taken from the
+    reconstruction `rec` (tight planes, before deblocking), leaves 0 .. 255 on both sides"""
+    n_both = 0
+    for plane, x0, y0, n, mode in intra_blocks(lf_mi, W, H):
+        if mode != 9 or x0 == 0 or y0 == 0:
+            continue
+        r = rec[plane].astype(np.int32)
+        t = r[y0:y0 + n, x0 - 1][:, None] + r[y0 - 1, x0:x0 + n][None, :] - r[y0 - 1, x0 - 1]
+        n_both += bool((t < 0).any() and (t > 255).any())
+    return n_both
+
+
+def intra_golden_reach(cases, gold, say=lambda *a: None):
+    """the conditions on the recorded data itself (the reference's, not any kernel's); returns the measured figures"""
+    sizes, n_tm, q0_full, shapes = set(), 0, 0, set()
+    for name, W, H, seed, q, kind in cases:
+        g = gold[name]
+        mi = np.frombuffer(g["mi"].tobytes(), B.LF_MODE_INFO_DTYPE).reshape(H // 8, W // 8)
+        sizes |= {n for p, _, _, n, _ in intra_blocks(mi, W, H) if p == 0}
+        tm = tm_blocks_clamped_both_ways(intra_planes(g["rec"], W, H), mi, W, H)
+        n_tm += tm
+        shapes.add(((H + 15) // 16, (W + 15) // 16))
+        mq, mdq, me = (int(np.abs(g[k].astype(np.int32)).max()) for k in ("qcoeff", "dqcoeff", "eob_map"))
+        say(f"{name}: {W}x{H} q {q} {kind}: max |qcoeff| {mq}, max |dqcoeff| {mdq}, max eob {me}, non-zero eobs {int((g['eob_map'] != 0).sum())}, TM blocks clamped both ways {tm}")
+        if q == 0:
+            assert mq >= 1000, (name, mq)
+            q0_full += me == 1024
+        if q == 255:
+            assert mq <= 16 and g["eob_map"].any(), (name, mq)
+    assert sizes == {4, 8, 16, 32}, sizes
+    assert q0_full >= 1, "no q 0 case with a full 32x32 block"
+    assert n_tm >= 1, "no TM block that clamps on both sides"
+    return dict(tm_both=n_tm, q0_full=q0_full, cell_grids=sorted(shapes))
 
 
 def oracle_intra_chain(src, lf_mi, q_index, flags, thr, pad=PAD, recon_init=None):

@@ -61,9 +61,9 @@ def run_intra(ctx, src, mi, q_index, flags, thr, rec_init, want_pred=True):
                 emap=emap_t.cpu().numpy().view(np.uint16), lfm=lfm_t.cpu().numpy(), lf=lf_t.cpu().numpy().view(B.LF_MODE_INFO_DTYPE).reshape(mi.shape))
 
 
-def check(ctx, W, H, seed, q_index, cfg, sizes=(8, 16, 32), modes=tuple(range(10)), mi_stride=None, quality=True):
+def check(ctx, W, H, seed, q_index, cfg, sizes=(8, 16, 32), modes=tuple(range(10)), mi_stride=None, quality=True, src=None):
     lib = B.load()
-    src = T.gen_yuv(W, H, seed)
+    src = T.gen_yuv(W, H, seed) if src is None else src
     level = lib.svt_hip_lf_level_from_q(lib.svt_hip_vp9_ac_step(q_index), 1)
     mi = M.gen_intra_grid(seed, W, H, sizes=sizes, modes=modes, filter_level=level, mi_stride=mi_stride)
     if mi_stride:

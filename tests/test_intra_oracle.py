@@ -3,8 +3,10 @@
     that read the above-right samples;
   * whole intra pictures through oracle/_ref/ref_intra: generate_intra_reference_samples + intra_prediction + perform_coding_loop +
     the neighbour-array writer, block by block in the reference's coding order.
-CPU only; skipped where the reference build is absent (the GPU box has the prebuilt files)."""
+CPU only; skipped where the reference build is absent -- except the recorded reference at the end (tests/golden/intra_reference.npz: thin
+pictures and the ends of the q range through ref_intra), which the oracle is compared with wherever the suite runs."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -136,3 +138,45 @@ def test_intra_blocks_of_inter_pictures_match_reference(W, H, seed, q):
         assert np.array_equal(got["rec"].interior()[k][~m], inter_rec[k][~m])                # inter blocks untouched
     assert np.array_equal(got["qcoeff"], want["qcoeff"]) and np.array_equal(got["dqcoeff"], want["dqcoeff"])
     assert np.array_equal(got["eob_map"], want["eob_map"]) and want["eob_map"].any()
+
+
+# ---- the recorded reference (tests/golden/intra_reference.npz, written by tests/gen_golden_intra.py): thin pictures and the ends of the q range ----
+GOLDEN_IDS = [c[0] for c in M.INTRA_GOLDEN_CASES]
+
+
+def _oracle_of(case):
+    src, mi = M.intra_golden_inputs(case)
+    return src, mi, M.intra_flat(M.oracle_intra_picture(src, mi, case[4]))
+
+
+@pytest.mark.parametrize("case", M.INTRA_GOLDEN_CASES, ids=GOLDEN_IDS)
+def test_oracle_equals_the_recorded_reference(case):
+    """always runs: the fixture holds what the reference's functions made of the case, and the inputs it was given"""
+    want = M.intra_golden()[case[0]]
+    src, mi, got = _oracle_of(case)
+    assert np.array_equal(np.concatenate([p.ravel() for p in src]), want["src"]), "the content generator no longer gives the recorded source"
+    assert np.ascontiguousarray(mi).tobytes() == want["mi"].tobytes(), "the grid generator no longer gives the recorded grid"
+    for k in M.INTRA_GOLDEN_KEYS:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (case[0], k, np.nonzero(got[k] != want[k])[0][:8].tolist())
+
+
+@pytest.mark.skipif(not T.have_ref("ref_intra"), reason="reference harness not built")
+@pytest.mark.parametrize("case", M.INTRA_GOLDEN_CASES, ids=GOLDEN_IDS)
+def test_oracle_and_fixture_equal_the_live_reference(case):
+    src, mi, got = _oracle_of(case)
+    live = M.intra_flat(M.ref_intra_picture(src, mi, case[4]))
+    gold = M.intra_golden()[case[0]]
+    for k in M.INTRA_GOLDEN_KEYS:
+        assert np.array_equal(got[k], live[k]), (case[0], k)
+        assert np.array_equal(gold[k], live[k]), (case[0], k, "the fixture is stale: python tests/gen_golden_intra.py")
+
+
+def test_recorded_reference_reaches_what_it_is_there_for():
+    """conditions on the reference's data, not on any kernel: the union of block sizes is {4, 8, 16, 32}; every q 0 case has max |qcoeff| >= 1000
+    and at least one a full 32x32 block (eob 1024); every q 255 case has max |qcoeff| <= 16 and non-zero eobs; TM blocks whose unclamped
+    left + above - corner (from the recorded reconstruction) leaves 0 .. 255 on both sides occur; the cell grids include min(rows, cols) of 1, 2, 3"""
+    gold = M.intra_golden()
+    assert list(gold) == GOLDEN_IDS
+    reach = M.intra_golden_reach(M.INTRA_GOLDEN_CASES, gold)
+    assert {min(s) for s in reach["cell_grids"]} >= {1, 2, 3} and (1, 1) in reach["cell_grids"]
+    assert os.path.getsize(M.INTRA_GOLDEN) < 400 * 1000
