@@ -656,7 +656,16 @@ typedef struct svt_mc_mode_info {
  * at least 64 + 16 samples around the luma picture and half of it around chroma, Codec/EbEncHandle.c:968-970: a
  * clamped MV reaches bw + 4 samples beyond the edge and the filter 4 more); pred = the prediction picture (sample
  * (0,0) pointers).  use_subpel = context_ptr->use_subpel_flag (0: the MVs are rounded to full samples the way
- * vp9_reconinter.c:175-188 does).  All pointers are device pointers. */
+ * vp9_reconinter.c:175-188 does).  All pointers are device pointers.
+ * What is read of a reference plane of W x H samples (luma, or chroma with its halved sizes), for a block of bw x bh samples of
+ * that plane: rows -(bh + 7) .. H + bh + 6, and in each of them the bytes -(bw + 10) .. W + bw + 11 relative to the row's sample 0.
+ * Rows are fetched as 16 aligned-down bytes around the 11 samples a 4-sample tile needs, so the fetch begins up to 3 bytes before
+ * the first of them and ends up to 5 bytes after the last.  With 64x64 blocks that is rows -71 .. H + 70 and bytes -74 .. W + 75 in luma,
+ * inside the padding of 80; in chroma (32x32, padding 40) it is rows -39 .. H + 38 but bytes -42 .. W + 43, so the first and last
+ * bytes of a fetch can belong to the neighbouring row's padding: the padded plane must be one allocation, rows stride apart, which the
+ * reference's buffers are.  No byte before the padded plane's first or after its last is read (tests/test_mc_model.py).
+ * MVs are VP9's: MV_LOW .. MV_UPP = -16384 .. 16383.  Beyond that a luma MV wraps the way the reference's does when it is scaled
+ * into int16 sixteenths (vp9_reconinter.c:76), e.g. 32767 becomes -2; nothing is read out of bounds for any int16 value. */
 typedef struct svt_mc_picture {
     const svt_mc_mode_info *d_mi;
     int32_t        mi_stride, mi_rows, mi_cols;

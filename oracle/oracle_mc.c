@@ -10,7 +10,7 @@
  *                                         specification; eb_vp9_filter_kernels[0] is hard-wired, vp9_reconinter.c:107-109)
  *   mb_to_*_edge                          Source/Lib/Codec/EbEncDecProcess.c:3708-3719
  * Pinned against the reference's own inter_prediction() built from source (oracle/_ref/ref_mc_frame,
- * tests/test_oracle_vs_ref.py) and against tests/golden/mc_reference.npz produced by it.
+ * tests/test_mc.py) and against tests/golden/mc_reference.npz and mc_edges_reference.npz produced by it.
  */
 #include <string.h>
 #include "oracle.h"
@@ -93,7 +93,9 @@ int32_t svt_oracle_inter_pred_frame(const svt_mc_mode_info *mi, int32_t mi_strid
                     const int spel_left = (4 + bw) << 4, spel_right = spel_left - 16;
                     const int spel_top = (4 + bh) << 4, spel_bottom = spel_top - 16;
                     const int sc = 1 << (1 - ss);
-                    int mv_row = m->mv_row[k] * sc, mv_col = m->mv_col[k] * sc;
+                    /* MV clamped_mv = {row * (1 << (1 - ss_y)), ...}: the products are stored in int16 fields, so luma MVs
+                     * beyond +-16383 (outside MV_LOW .. MV_UPP, which VP9 cannot code) wrap before they are clamped */
+                    int mv_row = (int16_t)(m->mv_row[k] * sc), mv_col = (int16_t)(m->mv_col[k] * sc);
                     mv_col = clampi(mv_col, to_left * sc - spel_left, to_right * sc + spel_right);
                     mv_row = clampi(mv_row, to_top * sc - spel_top, to_bottom * sc + spel_bottom);
                     /* vp9_reconinter.c:150-166: chroma positions use ROUND_UV() = multiples of 8 luma samples (always true here) */

@@ -147,7 +147,8 @@ __device__ __forceinline__ void mc_unit(const mc_pic_dev &P, int plane, int mi_r
     const int nref = rl1 >= 0 ? 2 : 1;
     for (int k = 0; k < nref; k++) {
         const svt_yuv_planes &R = P.ref[(k ? rl1 : rl0) ? 1 : 0];
-        int mv_row = (int16_t)(k ? m0 >> 16 : m0 & 0xffff) * sc, mv_col = (int16_t)(k ? m1 >> 16 : m1 & 0xffff) * sc;
+        /* the reference scales into an MV, a pair of int16 (vp9_reconinter.c:76): luma MVs beyond +-16383, which VP9 cannot code, wrap */
+        int mv_row = (int16_t)((int16_t)(k ? m0 >> 16 : m0 & 0xffff) * sc), mv_col = (int16_t)((int16_t)(k ? m1 >> 16 : m1 & 0xffff) * sc);
         mv_col = clampi(mv_col, to_left * sc - spel_left, to_right * sc + spel_right);
         mv_row = clampi(mv_row, to_top * sc - spel_top, to_bottom * sc + spel_bottom);
         int s_row, s_col, sx, sy;

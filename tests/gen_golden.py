@@ -105,6 +105,25 @@ def gen_mc():
     np.savez_compressed(os.path.join(G, "mc_reference.npz"), **mc)
 
 
+def gen_mc_edges():
+    # ---- inter prediction, constructed edge cases (svt_testlib.MC_EDGE_CASES): the reference's inter_prediction(), which the
+    # oracle must already equal wherever a block is predicted ----
+    assert T.have_ref("ref_mc_frame")
+    out = {}
+    for name in T.MC_EDGE_CASES:
+        refs = []
+        for case in T.make_mc_edge_case(name):
+            r, o = T.ref_mc_frame(case), T.oracle_mc_frame(case)
+            for p, a, b, m in zip("yuv", o, r, T.mc_inter_masks(case)[:1] + T.mc_inter_masks(case)[1:] * 2):
+                assert np.array_equal(a[m], b[m]), (case["key"], p)
+                assert not b[~m].any()
+            refs.append(r)
+        out.update(T.mc_edge_pack(name, refs))
+    path = os.path.join(G, "mc_edges_reference.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 512 * 1024, os.path.getsize(path)
+
+
 def gen_rate():
     # ---- coefficient rate estimation: the reference's tables (token costs of the default coefficient probabilities, value
     # / cat6 cost tables, scan orders with neighbours) and its coeff_rate_estimate() on the blocks of tests/test_rate.py ----
@@ -196,7 +215,7 @@ def gen_encdec_flags():
     np.savez_compressed(os.path.join(G, "encdec_flags_reference.npz"), flags=T.ref_encdec_flags())
 
 
-SECTIONS = ("scan", "me", "tq", "lf", "lf_extremes", "lf_masks", "mc", "rate", "quant", "ivf", "lf_params", "me_presets", "sad_loop", "sb_stats", "api", "refpad", "avg_ssd", "pd_split", "encdec_flags", "qp_scaling")
+SECTIONS = ("scan", "me", "tq", "lf", "lf_extremes", "lf_masks", "mc", "mc_edges", "rate", "quant", "ivf", "lf_params", "me_presets", "sad_loop", "sb_stats", "api", "refpad", "avg_ssd", "pd_split", "encdec_flags", "qp_scaling")
 
 
 def main():

@@ -1,5 +1,6 @@
 """Shared helpers for tests/, bench.py and __graft_entry__.smoke(): synthetic clips, PA planes,
 loading the product binding and the parity oracle (oracle/ is test infrastructure; see oracle/oracle_me.c)."""
+import collections
 import ctypes as C
 import glob
 import importlib.util
@@ -1271,8 +1272,252 @@ def mc_inter_masks(case):
     return np.kron(inter, np.ones((8, 8), bool)), np.kron(inter, np.ones((4, 4), bool))
 
 
+# ---- inter prediction: constructed edge cases (coverage facts come from tests/mc_model.py) ---------------------
+MC_EDGE_CASES = ("phases", "wave_modes", "ceilings", "flat", "clamps", "thin")
+MC_EDGE_GOLD = os.path.join(GOLDEN_DIR, "mc_edges_reference.npz")
+# the partitions from 8x8 to 64x64 as (bw8, bh8): BLOCK_8X8 .. BLOCK_64X64, the 10 of the reference's 13 BLOCK_SIZES that inter
+# prediction accepts (the other three are below 8x8)
+MC_BLOCK_SIZES = ((1, 1), (1, 2), (2, 1), (2, 2), (2, 4), (4, 2), (4, 4), (4, 8), (8, 4), (8, 8))
+_mc_edge_cache = {}
+
+
+def _mc_pic(key, mi, refs, use_subpel, pad=80, **extra):
+    mi_rows, mi_cols = mi.shape
+    return dict(key=key, mi=mi, mi_rows=mi_rows, mi_cols=mi_cols, refs=refs, pad=pad, use_subpel=use_subpel, width=mi_cols * 8, height=mi_rows * 8, **extra)
+
+
+def _mc_noise_refs(seed, width, height, pad=80):
+    """two reference pictures of independent random samples (textured in both directions at every scale), borders replicated"""
+    rng = np.random.default_rng(seed)
+    return [tuple(np.ascontiguousarray(np.pad(rng.integers(0, 256, (height >> s, width >> s), dtype=np.uint8), pad >> s, mode="edge")) for s in (0, 1, 1))
+            for _ in range(2)]
+
+
+def _mc_framed_refs(seed, width, height, pad=80):
+    """Reference pictures for clamped MVs: a frame of 4 random luma samples along the picture edges, and everywhere else -- the
+    padding included -- a pattern of period 8.  The padding is deliberately not a replica of the edge: a position beyond the clamp
+    bound predicts the same samples from a replicated border (that is why the reference may clamp), so only a padding that varies
+    shows where the bound lies.  Periodic content keeps the recorded planes of the many such pictures small."""
+    rng = np.random.default_rng(seed)
+    refs = []
+    for l in range(2):
+        planes = []
+        for s in (0, 1, 1):
+            p, f, w, h = pad >> s, 4 >> s, width >> s, height >> s
+            yy, xx = np.mgrid[-p:h + p, -p:w + p]
+            a = (((xx + 3 * l) & 7) * 29 + ((yy + 5 * l) & 7) * 3 + 7).astype(np.uint8)
+            frame = np.ones((h, w), bool)
+            frame[f:h - f, f:w - f] = False
+            a[p:p + h, p:p + w][frame] = rng.integers(0, 256, int(frame.sum()), dtype=np.uint8)
+            planes.append(np.ascontiguousarray(a))
+        refs.append(tuple(planes))
+    return refs
+
+
+def _mc_grid(mi_rows, mi_cols, bw8=1, bh8=1):
+    mi = np.zeros((mi_rows, mi_cols), dtype=B.MC_MODE_INFO_DTYPE)
+    mi["ref_list"] = -1
+    mi["bw8"], mi["bh8"] = bw8, bh8
+    return mi
+
+
+def _mc_edge_phases():
+    """one 8x8 unit per chroma class (sx, sy, load shift); the same MVs give luma its 8 x 8 x 4 classes"""
+    mi = _mc_grid(32, 32)
+    i = np.arange(1024).reshape(32, 32)
+    sx, sy, q = i & 15, (i >> 4) & 15, i >> 8
+    mi["ref_list"][:, :, 0] = (i >> 5) & 1
+    mi["mv_col"][:, :, 0] = sx + 16 * (q - 2)                # whole chroma samples -2 .. 1: the four load shifts
+    mi["mv_row"][:, :, 0] = sy + 16 * ((i * 7) % 5 - 2)
+    return [_mc_pic("phases", mi, _mc_noise_refs(901, 256, 256), 1)]
+
+
+# wave_modes: MV (row, col) of unit c (0..31) of a band row, variant v.  1/8 luma sample = 1/16 chroma sample: multiples of 16 are
+# full-sample for both planes, odd multiples of 8 for luma only.
+def _wm_disp(c):
+    return 16 * (c % 3 - 1), 16 * (c % 4 - 2)
+
+
+_WM_PATTERNS = {
+    "horz": lambda c, v: (16 * (c % 3 - 1), (c & 15) + 16 * (2 * v + (c >> 4) - 2)),
+    "vert": lambda c, v: ((c & 15) + 16 * (c % 3 - 1), 16 * (2 * v + (c >> 4) - 2) if v < 2 else 8 * (2 * ((c >> 3) & 3) - 3)),
+    "copy": lambda c, v: _wm_disp(c) if v == 0 else (8 * (2 * (c % 3) - 3), 8 * (2 * ((c >> 3) & 3) - 3)),
+    "full": lambda c, v: (((c * 5 + 3 * v) & 15) + 16 * (c % 3 - 1), (c & 15) + 16 * (2 * v + (c >> 4) - 2)),
+    "one_horz": lambda c, v: (_wm_disp(c)[0], _wm_disp(c)[1] + (3 if c == 13 else 0)),
+    "one_vert": lambda c, v: (_wm_disp(c)[0] + (5 if c == 21 else 0), _wm_disp(c)[1]),
+    "reverse": lambda c, v: (16, -32) if c == 7 else (1 + c % 7 + 16 * (c % 3 - 1), 9 + (c * 3) % 7 - 16 * (c & 1)),
+}
+# (band, pattern and variant of reference 0, of reference 1 or None)
+_WM_ROWS = ([("horz", ("horz", v), None) for v in (0, 1)] + [("vert", ("vert", v), None) for v in (0, 1, 2)] + [("copy", ("copy", v), None) for v in (0, 1)] +
+            [("full", ("full", v), None) for v in (0, 1)] + [(n, (n, 0), None) for n in ("one_horz", "one_vert", "reverse")] +
+            [("c_horz_vert", ("horz", 0), ("vert", 0)), ("c_vert_copy", ("vert", 1), ("copy", 0)), ("c_copy_full", ("copy", 1), ("full", 0)),
+             ("c_full_horz", ("full", 1), ("horz", 1)), ("c_one_horz_one_vert", ("one_horz", 0), ("one_vert", 0)),
+             ("c_one_vert_reverse", ("one_vert", 0), ("reverse", 0)), ("c_reverse_copy", ("reverse", 0), ("copy", 0))])
+
+
+def _mc_edge_wave_modes():
+    """256 wide: one mode-info row is one workgroup, so a row of MVs decides what its two waves do"""
+    mi = _mc_grid(len(_WM_ROWS), 32)
+    bands = {}
+    for r, (band, p0, p1) in enumerate(_WM_ROWS):
+        bands.setdefault(band, []).append(r)
+        for c in range(32):
+            mi["ref_list"][r, c] = ((r + c) & 1, -1 if p1 is None else 1 - ((r + c) & 1))
+            for k, p in enumerate((p0, p1)):
+                if p is not None:
+                    mi["mv_row"][r, c, k], mi["mv_col"][r, c, k] = _WM_PATTERNS[p[0]](c, p[1])
+    refs = _mc_noise_refs(902, 256, 8 * len(_WM_ROWS))
+    return [_mc_pic(f"wave_modes|{sub}", mi, refs, sub, bands=bands) for sub in (1, 0)]
+
+
+# 255 under every positive tap and 0 under every negative one, for every phase (taps that are 0 in some phases do not matter)
+MC_CEILING_SIGNS = np.array([0, 1, 0, 1, 1, 0, 1, 0], bool)
+
+
+def _mc_edge_ceilings():
+    """0 / 255 planes, built with their padding: sample (y, x) is 255 where the sign pattern at x equals the one at y.  A window
+    that starts at a multiple of 8 then sees 255 under the positive taps in the rows where the pattern is set and under the
+    negative taps in the others, so the horizontal pass clips at 255 resp. 0 and leaves the same pattern down that column for
+    the vertical pass.  List 1 holds the inverse picture."""
+    pad, n = 80, 64
+    planes = []
+    for s in (0, 1, 1):
+        p = pad >> s
+        sg = MC_CEILING_SIGNS[(np.arange((n >> s) + 2 * p) - p) % 8]
+        planes.append(np.ascontiguousarray(np.where(sg[:, None] == sg[None, :], 255, 0).astype(np.uint8)))
+    refs = [tuple(planes), tuple(np.ascontiguousarray(255 - a) for a in planes)]
+    mi = _mc_grid(8, 8)
+    i = np.arange(64).reshape(8, 8)
+    rr, cc = i >> 3, i & 7
+    mi["ref_list"][:, :, 0] = i & 1
+    # whole chroma samples 3 (even units) / -1 (odd units): the window of the unit's first chroma sample starts at a multiple of 8
+    mi["mv_col"][:, :, 0] = (i * 5 + 1) % 16 + 16 * np.where(cc & 1, -1, 3)
+    mi["mv_row"][:, :, 0] = (i >> 1) % 16 + 16 * np.where(rr & 1, -1, 3)
+    return [_mc_pic("ceilings", mi, refs, 1)]
+
+
+def _mc_edge_flat():
+    """flat planes of 0, 255, 127 and 128 under all 256 phase pairs, single and compound: every sum restores the bias exactly"""
+    pics = []
+    for val in (0, 255, 127, 128):
+        refs = [tuple(np.full((128 + 160 >> s, 128 + 160 >> s), val, np.uint8) for s in (0, 1, 1)) for _ in range(2)]
+        mi = _mc_grid(16, 16)
+        i = np.arange(256).reshape(16, 16)
+        mi["ref_list"][:, :, 0] = i & 1
+        mi["ref_list"][:, :, 1] = np.where(i % 3 == 0, 1 - (i & 1), -1)
+        mi["mv_col"][:, :, 0], mi["mv_row"][:, :, 0] = (i & 15) - 16, (i >> 4) + 16
+        mi["mv_col"][:, :, 1], mi["mv_row"][:, :, 1] = (i >> 4) + 32, (i & 15) - 32
+        pics.append(_mc_pic(f"flat|{val}", mi, refs, 1, flat=val))
+    return pics
+
+
+MC_CLAMP_DIRS = ("L", "R", "T", "B", "TL", "TR", "BL", "BR")
+# MVs of one direction: (plane whose clamp bound is meant, steps of 1/8 sample beyond it) or an int16 extreme
+MC_CLAMP_KINDS = (("y", -1), ("y", 0), ("y", 1), ("c", -1), ("c", 0), ("c", 1), "extreme")
+
+
+def _mc_clamp_mv(model, mi_rows, mi_cols, r, c, bw8, bh8, side, kind):
+    """the MV component (1/8 luma sample) of `kind` towards `side` for the block at (r, c); the bounds are the model's"""
+    out = -1 if side in "LT" else 1
+    if kind == "extreme":
+        return -32768 if out < 0 else 32767
+    plane, step = kind
+    bounds, scale = model.clamp_bounds(mi_rows, mi_cols, r, c, bw8, bh8, 0 if plane == "y" else 1)
+    b = bounds["LRTB".index(side)]
+    assert b % scale == 0
+    return b // scale + out * step
+
+
+def _mc_edge_clamps():
+    """every block size against every picture side and corner, with MVs at, one step inside and one step beyond the clamp bound of
+    each plane and at the int16 extremes; single blocks carry one such MV, compound blocks two different ones.  Blocks that do
+    not touch a side, or are left over, are intra."""
+    import mc_model as model
+    dims = ((128, 128), (64, 192))
+    refs = {d: _mc_framed_refs(904 + i, *d) for i, d in enumerate(dims)}
+    pics = []
+    for (bw8, bh8) in MC_BLOCK_SIZES:
+        nk = len(MC_CLAMP_KINDS)
+        todo = [(d, (j,)) for d in MC_CLAMP_DIRS for j in range(nk)] + [(d, (j % nk, (j + 3) % nk)) for j, d in enumerate(MC_CLAMP_DIRS)]
+        n = 0
+        while todo:
+            W, H = dims[n % 2]
+            R, C = H // 8, W // 8
+            mi = _mc_grid(R, C, bw8, bh8)
+            for r in range(0, R, bh8):
+                for c in range(0, C, bw8):
+                    touch = ("L" if c == 0 else "") + ("R" if c + bw8 == C else "") + ("T" if r == 0 else "") + ("B" if r + bh8 == R else "")
+                    pick = next((t for t in todo if all(s in touch for s in t[0])), None)
+                    if pick is None:
+                        continue
+                    todo.remove(pick)
+                    d, kinds = pick
+                    cell = np.zeros((), dtype=B.MC_MODE_INFO_DTYPE)
+                    cell["bw8"], cell["bh8"] = bw8, bh8
+                    l0 = (r // bh8 + c // bw8) & 1
+                    cell["ref_list"] = (l0, 1 - l0 if len(kinds) == 2 else -1)
+                    for k, kind in enumerate(kinds):
+                        mv = {"row": 3 - 8 * k, "col": 8 * k - 5}          # the component along a side that is not aimed at: small
+                        for s in d:
+                            mv["col" if s in "LR" else "row"] = _mc_clamp_mv(model, R, C, r, c, bw8, bh8, s, MC_CLAMP_KINDS[kind])
+                        cell["mv_row"][k], cell["mv_col"][k] = mv["row"], mv["col"]
+                    mi[r:r + bh8, c:c + bw8] = cell
+            for sub in (1, 0):
+                pics.append(_mc_pic(f"clamps|{bw8}x{bh8}|{n}|{sub}", mi, refs[(W, H)], sub))
+            n += 1
+            assert n < 64
+    return pics
+
+
+def _mc_edge_thin():
+    """the smallest pictures, every MV far outside: up-left / down-right / up-right / down-left, two of them in every (compound) block"""
+    far = ((-2000, -3000), (2900, 2100), (-2500, 2700), (3100, -1900))
+    pics = []
+    for (W, H) in ((8, 8), (8, 64), (64, 8), (16, 16)):
+        refs = _mc_noise_refs(905 + W + 3 * H, W, H)
+        for v in (0, 1):
+            big = (W, H) == (16, 16) and v == 0
+            mi = _mc_grid(H // 8, W // 8, 2 if big else 1, 2 if big else 1)
+            for r in range(H // 8):
+                for c in range(W // 8):
+                    i = 0 if big else r + c
+                    mi["ref_list"][r, c] = (i & 1, 1 - (i & 1))
+                    for k in (0, 1):
+                        mi["mv_row"][r, c, k], mi["mv_col"][r, c, k] = far[(2 * v + k + 2 * (i & 1) + (i >> 1)) % 4]
+            pics.append(_mc_pic(f"thin|{W}x{H}|{v}", mi, refs, 1 - v))
+    return pics
+
+
+def make_mc_edge_case(name):
+    """The pictures (dicts like make_mc_case's, plus a unique "key") of one constructed inter-prediction case.  What each is built
+    to reach is asserted by tests/test_mc_model.py from the model in tests/mc_model.py.  Cached: treat the result as read-only."""
+    if name not in _mc_edge_cache:
+        _mc_edge_cache[name] = {"phases": _mc_edge_phases, "wave_modes": _mc_edge_wave_modes, "ceilings": _mc_edge_ceilings, "flat": _mc_edge_flat,
+                                "clamps": _mc_edge_clamps, "thin": _mc_edge_thin}[name]()
+    return _mc_edge_cache[name]
+
+
+def mc_edge_pack(name, outs):
+    """the predictions of a case's pictures ([y, u, v] each, in order) as fixture entries: pictures of one size are stacked"""
+    d = {}
+    for pic, planes in zip(make_mc_edge_case(name), outs):
+        for p, a in zip("yuv", planes):
+            d.setdefault(f"{name}|{p}|{pic['width']}x{pic['height']}", []).append(a)
+    return {k: np.stack(v) for k, v in d.items()}
+
+
+def mc_edge_unpack(g, name):
+    """inverse of mc_edge_pack: [y, u, v] per picture of the case from the loaded fixture g"""
+    seen, outs = collections.Counter(), []
+    for pic in make_mc_edge_case(name):
+        dims = f"{pic['width']}x{pic['height']}"
+        outs.append([g[f"{name}|{p}|{dims}"][seen[dims]] for p in "yuv"])
+        seen[dims] += 1
+    return outs
+
+
 # ---- coefficient rate estimation ---------------------------------------------------------------------------------
-RATE_GOLD = os.path.join(GOLDEN_DIR, "rate_reference.npz")
+RATE_GOLD =os.path.join(GOLDEN_DIR, "rate_reference.npz")
 
 
 def _rate_request(case):

@@ -43,6 +43,23 @@ def test_oracle_vs_golden(seed, w, h, sub):
     _check(T.oracle_mc_frame(case), [g[f"{p}|{seed}|{w}|{h}|{sub}"] for p in "yuv"], case)
 
 
+@live
+@pytest.mark.parametrize("name", T.MC_EDGE_CASES)
+def test_oracle_vs_reference_edge_cases(name):
+    """the constructed cases (wave modes, filter ceilings, clamp bounds, thin pictures) against the reference itself"""
+    for case in T.make_mc_edge_case(name):
+        _check(T.oracle_mc_frame(case), T.ref_mc_frame(case), case)
+
+
+@pytest.mark.parametrize("name", T.MC_EDGE_CASES)
+def test_oracle_vs_golden_edge_cases(name):
+    g = np.load(T.MC_EDGE_GOLD)
+    cases = T.make_mc_edge_case(name)
+    for case, ref in zip(cases, T.mc_edge_unpack(g, name)):
+        _check(T.oracle_mc_frame(case), ref, case)
+    assert sum(g[k].shape[0] for k in g.files if k.startswith(name + "|y|")) == len(cases)  # the fixture holds these pictures and no others
+
+
 def test_phase0_is_identity_and_compound_rounds_up():
     """zero MVs: single-list blocks copy the reference, compound blocks are (a + b + 1) >> 1"""
     case = T.make_mc_case(21, width=64, height=64, rect=False, intra_share=0.0)
