@@ -840,7 +840,7 @@ uint32_t svt_hip_tokenize_capacity(int32_t width, int32_t height);
  *                 d_bools + first.  Segments are coded in list order; a transform block never straddles two segments.
  * The tables are the caller's data (the frame's coefficient probabilities and the two constant tables of VPX/vp9_entropy.c),
  * uploaded once per context.  The raw bools and the segment list of a tile come from the mode-info stages below (key frames:
- * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device behind svt_hip_mvrefs_batch_device); the
+ * svt_hip_modes_kf_batch_device, inter pictures: svt_hip_modes_inter_batch_device behind svt_hip_md_inter_modes_batch_device); the
  * uncompressed and compressed headers and the packet around the tile are the frame stage's (svt_hip_frame_header_host,
  * svt_hip_frame_batch_device); delivery through libSvtVp9Enc.so is not here yet. */
 typedef struct svt_bool_tables {
@@ -958,7 +958,7 @@ uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height);
  * (VPX/vp9_pred_common.c) and is taken from the grid (csrc/modeinfo_inter_core.h).  Chain: encode pass -> tokeniser -> this -> bool
  * coder on one context's stream, no host round trip.  mbmi_ext's values -- the MV references and the mode context that
  * eb_vp9_find_mv_refs derives -- are inputs here exactly as they are inputs of pack_inter_mode_mvs; svt_hip_mvrefs_batch_device below
- * derives them on the device.  The two headers and the packet around the tile are the frame stage's (svt_hip_frame_header_host,
+ * derives them on the device, and svt_hip_md_inter_modes_batch_device produces the whole records from the encode pass's grids.  The two headers and the packet around the tile are the frame stage's (svt_hip_frame_header_host,
  * svt_hip_frame_batch_device); delivery through libSvtVp9Enc.so is not here yet.
  *
  * The tables are the caller's data (the frame context cm->fc), uploaded once per context. */
@@ -1078,6 +1078,52 @@ typedef struct svt_mvrefs_picture {
 int32_t svt_hip_mvrefs_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_mvrefs_picture *pics, int32_t width, int32_t height, int32_t mi_stride);
 /* host form of the same text (csrc/mvrefs_core.h), pure CPU, host pointers */
 int32_t svt_hip_mvrefs_picture(const svt_mvrefs_picture *pic, int32_t width, int32_t height, int32_t mi_stride);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Inter mode labelling: the two grids the encode pass holds -> complete svt_mi_inter_ext records, the producer the two entries above
+ * lacked.  ref_frame of every unit follows from the prediction grid's ref_list; the inter mode of every leaf is chosen so that it
+ * agrees with the leaf's MVs -- NEARESTMV if every reference's MV is the first candidate eb_vp9_find_mv_refs derives (and one was
+ * found), else NEARMV if it is the second (and two were found), else ZEROMV if every MV is zero, else NEWMV -- in that fixed order,
+ * not by rate (csrc/md_inter_core.h says why); mode_context and ref_mv_* are then derived from the labelled grid exactly as
+ * svt_hip_mvrefs_batch_device derives them, which by construction counts no contradiction in these records.  Chain: encode pass ->
+ * tokeniser -> this -> inter mode info -> bool coder -> frame on one context's stream, no host round trip: d_ext_out is the d_ext of
+ * svt_hip_modes_inter_batch_device.
+ *
+ * one picture of a batch; every pointer is a device pointer (host pointers in the host form); the grids share one mi_stride.
+ *   d_lf_mi, d_mc_mi   sb_type and is_inter; ref_list and mv_row / mv_col of ref 0 / 1 (not read for an intra unit)
+ *   d_ext_out   WRITTEN, one complete record per unit of the picture, in svt_hip_mvrefs_batch_device's format: ref_frame at every unit
+ *               ({0, 0} at an intra one); at an inter leaf's origin mode, ref_mv_row / ref_mv_col[k] and mode_context; every other
+ *               field 0
+ *   d_cand      WRITTEN (unless NULL) as svt_hip_mvrefs_batch_device writes it, for the reference frames of ref_mask
+ *   d_status    WRITTEN always, four words: {inter leaves, leaves labelled NEWMV, NEWMV leaves pack_inter_mode_mvs cannot code
+ *               faithfully -- a difference to ref_mv[k] beyond +-16383 in a component, or an odd one where the high-precision bit is
+ *               not coded (!(allow_hp && use_mv_hp(ref_mv[k]))): counted, not altered; a picture with a non-zero count must not be
+ *               shipped --, 0}; all four SVT_MODES_BAD_GRID for a grid this entry does not take: whatever svt_hip_mvrefs_batch_device
+ *               refuses, a ref_list above 1, list_ref_frame outside 1 .. 3, a compound leaf under SINGLE_REFERENCE (a single one
+ *               under COMPOUND_REFERENCE) or one whose references are not comp_fixed_ref plus one of comp_var_ref.  d_ext_out and
+ *               d_cand are then unspecified
+ *   list_ref_frame     the reference frame (1 .. 3) REF_LIST_0 / REF_LIST_1 stand for in this picture
+ *   the other parameters mean what they mean in svt_mvrefs_picture and svt_modes_inter_picture */
+typedef struct svt_md_inter_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const svt_mc_mode_info *d_mc_mi;
+    svt_mi_inter_ext       *d_ext_out;
+    svt_mvref_cand         *d_cand;
+    uint32_t               *d_status;
+    uint8_t                 list_ref_frame[2];
+    uint8_t                 ref_frame_sign_bias[4];
+    uint8_t                 restrict_ref_mvs, allow_hp, reference_mode, comp_fixed_ref, comp_var_ref[2];
+    uint8_t                 ref_mask;
+    uint8_t                 pad_[3];
+} svt_md_inter_picture;                     /* 56 bytes */
+/* n_pics (<= 32) pictures of one geometry (multiples of 8, 8 .. 8192, mi_stride >= width / 8) in one call; their parameters may
+ * differ.  Asynchronous on the context's stream, no synchronisation; scratch (12 bytes per unit of the batch) is taken from the context
+ * at the first call of a geometry.  Refused, nothing launched: a null required pointer, n_pics outside 1 .. 32, ref_mask with bit 0 or
+ * bits 4 .. 7 set, reference_mode above 2 or -- unless it is SINGLE_REFERENCE -- a compound reference outside 1 .. 3. */
+int32_t svt_hip_md_inter_modes_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_md_inter_picture *pics, int32_t width, int32_t height,
+                                            int32_t mi_stride);
+/* host form of the same text (csrc/md_inter_core.h), pure CPU, host pointers */
+int32_t svt_hip_md_inter_modes_picture(const svt_md_inter_picture *pic, int32_t width, int32_t height, int32_t mi_stride);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Picture-level EncDec: everything the encode pass does with mode decision's output, whole pictures at a time, device resident.

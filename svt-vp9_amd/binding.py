@@ -212,6 +212,15 @@ class MvrefsPicture(C.Structure):
                 ("ref_mask", C.c_uint8), ("restrict_ref_mvs", C.c_uint8), ("ref_frame_sign_bias", C.c_uint8 * 4), ("pad_", C.c_uint8 * 2)]
 
 
+# inter mode labelling (svt_md_inter_picture of include/svtvp9_hip.h)
+class MdInterPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_mc_mi", C.c_void_p), ("d_ext_out", C.c_void_p), ("d_cand", C.c_void_p), ("d_status", C.c_void_p),
+                ("list_ref_frame", C.c_uint8 * 2), ("ref_frame_sign_bias", C.c_uint8 * 4), ("restrict_ref_mvs", C.c_uint8), ("allow_hp", C.c_uint8),
+                ("reference_mode", C.c_uint8), ("comp_fixed_ref", C.c_uint8), ("comp_var_ref", C.c_uint8 * 2), ("ref_mask", C.c_uint8), ("pad_", C.c_uint8 * 3)]
+
+
+assert C.sizeof(MdInterPicture) == 56
+
 # frame stage (svt_frame_params / svt_frame_packet / svt_frame_entry of include/svtvp9_hip.h)
 FRAME_HEADER_MAX = 56
 FRAME_SIZE_NONE = 0xFFFFFFFF
@@ -273,6 +282,7 @@ EXPORTS = [
     "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
     "svt_hip_modes_inter_set_tables", "svt_hip_modes_inter_batch_device", "svt_hip_modes_inter_picture", "svt_hip_modes_inter_bools_capacity",
     "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
+    "svt_hip_md_inter_modes_batch_device", "svt_hip_md_inter_modes_picture",
     "svt_hip_frame_header_host", "svt_hip_frame_show_existing_host", "svt_hip_frame_batch_device", "svt_hip_frame_assemble_host", "svt_hip_frame_geometry",
 ]
 

@@ -222,6 +222,8 @@ SVT_HD int svt_mii_mv_bools(int drow, int dcol, int usehp, const svt_modes_inter
     return n;
 }
 SVT_HD int svt_mii_abs(int v) { return v < 0 ? -v : v; }
+/* use_mv_hp (VPX/vp9_entropymv.h): the high-precision bit of a difference is coded only against a reference MV below 8 samples */
+SVT_HD int svt_mii_use_mv_hp(int ref_row, int ref_col) { return svt_mii_abs(ref_row) < 64 && svt_mii_abs(ref_col) < 64; }
 
 /* 0: the unit (r, c) lies in a block this syntax takes -- what svt_mi_check asks of a key frame's unit but for is_inter, and:
  * ref_frame, is_inter and the prediction grid's ref_list agree about inter and compound; an inter block is 8x8 or larger; a compound
@@ -333,7 +335,7 @@ SVT_HD int svt_mii_unit_bools(const svt_mii_view *v, const svt_tok_geom *g, int 
     n += svt_mii_tree4(x->mode == 12 ? 0 : x->mode == 13 ? 3 : x->mode - 9, out ? t->inter_mode_probs[x->mode_context] : (const uint8_t *)0, out ? out + n : (uint16_t *)0);
     if (x->mode == 13)
         for (int k = 0; k <= comp; k++) {
-            const int usehp = v->f.allow_hp && svt_mii_abs(x->ref_mv_row[k]) < 64 && svt_mii_abs(x->ref_mv_col[k]) < 64; /* use_mv_hp (VPX/vp9_entropymv.h) */
+            const int usehp = v->f.allow_hp && svt_mii_use_mv_hp(x->ref_mv_row[k], x->ref_mv_col[k]);
             n += svt_mii_mv_bools(m->mv_row[k] - x->ref_mv_row[k], m->mv_col[k] - x->ref_mv_col[k], usehp, t, out ? out + n : (uint16_t *)0);
         }
     return n;

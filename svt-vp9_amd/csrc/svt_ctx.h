@@ -6,7 +6,7 @@
 #include <string.h>
 #include "../../include/svtvp9_hip.h"
 
-#define SVT_CTX_SLOTS 55
+#define SVT_CTX_SLOTS 57
 #define SVT_CTX_RING 64
 #define SVT_CTX_UPLOAD_RING 4   /* pinned staging buffers of svt_hip_mem_upload_2d_async */
 #define SVT_CTX_MARKERS 1024    /* completion markers in flight (svt_hip_ctx_marker_*) */
