@@ -30,10 +30,6 @@
 #define BC_K 256          /* bools per chunk */
 #define BC_TILE 32        /* chunks per LDS tile of the chain kernel */
 #define BC_ITEMS 1024     /* items per workgroup of count / expand: 256 lanes x 4 consecutive items */
-#define BC_SCRATCH_SLOT 46
-#define BC_TABLES_SLOT 47
-#define BC_IN_SLOT 48
-#define BC_OUT_SLOT 49
 
 extern "C" int32_t svt_boolcode_check_segments(uint32_t n_tokens, uint32_t n_bools, const svt_bool_segment *segments, uint32_t n_segments, uint64_t *items);
 
@@ -337,7 +333,7 @@ extern "C" int32_t svt_hip_boolcode_set_tables(svt_hip_ctx *ctx, const svt_bool_
     if (!ctx || !tables) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: null argument");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream)); /* (a call in flight may still read the tables) */
-    void *d = svt_ctx_slot(ctx, BC_TABLES_SLOT, sizeof(svt_bool_tables));
+    void *d = svt_ctx_slot(ctx, SVT_SLOT_BC_TABLES, sizeof(svt_bool_tables));
     if (!d) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: tables");
     HIP_TRY(hipMemcpyAsync(d, tables, sizeof(svt_bool_tables), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -363,9 +359,9 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
         max_chunks = chunks > max_chunks ? chunks : max_chunks;
         max_words = words > max_words ? words : max_words;
     }
-    if (!ctx->slot_bytes[BC_TABLES_SLOT]) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: svt_hip_boolcode_set_tables has not been called");
+    if (!ctx->slot_bytes[SVT_SLOT_BC_TABLES]) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: svt_hip_boolcode_set_tables has not been called");
     HIP_TRY(hipSetDevice(ctx->device));
-    uint8_t *scratch = (uint8_t *)svt_ctx_slot(ctx, BC_SCRATCH_SLOT, total);
+    uint8_t *scratch = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_BC_SCRATCH, total);
     if (!scratch) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: scratch");
     bc_batch_dev hb;
     memset(&hb, 0, sizeof hb);
@@ -391,7 +387,7 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
     HIP_TRY(hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
     svt_ctx_stage_commit(ctx);
     const bc_batch_dev    *dB = (const bc_batch_dev *)d;
-    const svt_bool_tables *dT = (const svt_bool_tables *)ctx->slot[BC_TABLES_SLOT];
+    const svt_bool_tables *dT = (const svt_bool_tables *)ctx->slot[SVT_SLOT_BC_TABLES];
     const dim3             ns((unsigned)n_streams);
     hipLaunchKernelGGL(svt_bc_segscan_kernel, ns, dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_count_kernel, dim3(max_tiles, n_streams), dim3(256), 0, ctx->stream, dB);
@@ -421,8 +417,8 @@ extern "C" int32_t svt_hip_boolcode(svt_hip_ctx *ctx, const uint32_t *tokens, ui
     if (7 * (max_bools + 1 + SVT_BOOL_FRAME_TAIL) >= 0x100000000ull) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: stream too long for 32-bit bit positions");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t tb = align16(sizeof(uint32_t) * (size_t)n_tokens), bb = align16(sizeof(uint16_t) * (size_t)n_bools), sb = align16(sizeof(svt_bool_segment) * (size_t)n_segments);
-    uint8_t     *din = (uint8_t *)svt_ctx_slot(ctx, BC_IN_SLOT, tb + bb + sb + 16);
-    uint8_t     *dout = (uint8_t *)svt_ctx_slot(ctx, BC_OUT_SLOT, 16 + (size_t)capacity);
+    uint8_t     *din = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_BC_IN, tb + bb + sb + 16);
+    uint8_t     *dout = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_BC_OUT, 16 + (size_t)capacity);
     if (!din || !dout) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: device buffers");
     if (n_tokens) HIP_TRY(hipMemcpyAsync(din, tokens, sizeof(uint32_t) * (size_t)n_tokens, hipMemcpyHostToDevice, ctx->stream));
     if (n_bools) HIP_TRY(hipMemcpyAsync(din + tb, bools, sizeof(uint16_t) * (size_t)n_bools, hipMemcpyHostToDevice, ctx->stream));

@@ -18,7 +18,7 @@ struct mi_stage {
     typedef svt_modes_picture       picture;
     typedef const svt_lf_mode_info *view;
     typedef svt_modes_tables        tables;
-    static constexpr int         UNIT_BOOLS = SVT_MI_UNIT_BOOLS, EMIT_WAVES = 4, SCRATCH_SLOT = 50, TABLES_SLOT = 51;
+    static constexpr int         UNIT_BOOLS = SVT_MI_UNIT_BOOLS, EMIT_WAVES = 4, SCRATCH_SLOT = SVT_SLOT_MI_SB_OFF, TABLES_SLOT = SVT_SLOT_MI_TABLES;
     static constexpr const char *NAME = "modes";
     static __device__ __forceinline__ int check(const view &v, const svt_tok_geom *g, int r, int c) { return svt_mi_check(v, g, r, c); }
     static __device__ __forceinline__ int unit_bools(const view &v, const svt_tok_geom *g, int r, int c, const tables *t, uint16_t *out) { return svt_mi_unit_bools(v, g, r, c, t, out); }

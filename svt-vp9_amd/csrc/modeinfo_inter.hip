@@ -20,7 +20,7 @@ struct mii_stage {
     typedef svt_modes_inter_picture picture;
     typedef svt_mii_view            view;
     typedef svt_modes_inter_tables  tables;
-    static constexpr int         UNIT_BOOLS = SVT_MII_UNIT_BOOLS, EMIT_WAVES = 2, SCRATCH_SLOT = 52, TABLES_SLOT = 53;
+    static constexpr int         UNIT_BOOLS = SVT_MII_UNIT_BOOLS, EMIT_WAVES = 2, SCRATCH_SLOT = SVT_SLOT_MII_SB_OFF, TABLES_SLOT = SVT_SLOT_MII_TABLES;
     static constexpr const char *NAME = "modes_inter";
     static __device__ __forceinline__ int check(const view &v, const svt_tok_geom *g, int r, int c) { return svt_mii_check(&v, g, r, c); }
     static __device__ __forceinline__ int unit_bools(const view &v, const svt_tok_geom *g, int r, int c, const tables *t, uint16_t *out) { return svt_mii_unit_bools(&v, g, r, c, t, out); }

@@ -19,6 +19,8 @@
  *
  *   svt_mvr_check    is the record of an 8x8 unit one this stage takes?
  *   svt_mvr_pack     the window entry of a unit: MV 0, MV 1 and a meta word
+ *   svt_mvr_window_unit / _no_entry / _window_put, svt_mvr_view_of   building a window position by position, and a picture's view: the
+ *                    text the device skeleton (mvrefs_stage.h) and the host forms share
  *   svt_mvr_derive   eb_vp9_find_mv_refs of one block and one reference frame: the two candidates, the return value
  *   svt_mvr_context  the mode context of a block (it does not depend on the reference frame)
  *   svt_mvr_unit     everything the stage writes for one unit
@@ -119,6 +121,28 @@ SVT_HD svt_mvr_entry svt_mvr_pack(const svt_mvr_view *v, const svt_tok_geom *g, 
         e.meta = 1u | 2u | (uint32_t)(r1 > 0) << 2 | (uint32_t)r0 << 3 | (uint32_t)r1 << 5 | (uint32_t)(mode == 12 ? 3 : mode == 13 ? 1 : 0) << 8;
     }
     return e;
+}
+/* building the window of the SB whose first unit is (sb_r, sb_c), position i = 0 .. 120 at a time: the picture unit of the position and
+ * whether it lies inside the picture; and the entry's three words at 3 * i -- a position outside the picture holds the zero entry (not
+ * "there").  What packs an entry is the caller's: svt_mvr_pack here, svt_mdi_pack before the records exist (md_inter_core.h) */
+SVT_HD int svt_mvr_window_unit(const svt_tok_geom *g, int sb_r, int sb_c, int i, int *r, int *c) {
+    *r = sb_r - 3 + i / SVT_MVR_WIN; *c = sb_c - 3 + i % SVT_MVR_WIN;
+    return *r >= 0 && *c >= 0 && *r < g->mi_rows && *c < g->mi_cols;
+}
+SVT_HD svt_mvr_entry svt_mvr_no_entry(void) {
+    svt_mvr_entry e;
+    e.mv0 = e.mv1 = e.meta = 0;
+    return e;
+}
+SVT_HD void svt_mvr_window_put(uint32_t *win, int i, svt_mvr_entry e) { win[3 * i] = e.mv0; win[3 * i + 1] = e.mv1; win[3 * i + 2] = e.meta; }
+/* the view of a picture from its descriptor's fields (svt_mvrefs_picture, svt_md_inter_picture) */
+SVT_HD svt_mvr_view svt_mvr_view_of(const svt_lf_mode_info *mi, const svt_mc_mode_info *mc, const svt_mi_inter_ext *ext, int ref_mask, int restrict_ref_mvs,
+                                    const uint8_t *ref_frame_sign_bias) {
+    svt_mvr_view v = {0};
+    v.mi = mi; v.mc = mc; v.ext = ext;
+    v.ref_mask = (uint8_t)ref_mask; v.restrict_ref_mvs = restrict_ref_mvs != 0;
+    for (int k = 0; k < 4; k++) v.sign_bias |= (uint8_t)((ref_frame_sign_bias[k] != 0) << k);
+    return v;
 }
 SVT_HD svt_mvr_entry svt_mvr_window_at(const uint32_t *win, int wr, int wc) {
     const uint32_t *p = win + 3 * (wr * SVT_MVR_WIN + wc);

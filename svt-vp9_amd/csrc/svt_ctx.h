@@ -6,7 +6,19 @@
 #include <string.h>
 #include "../../include/svtvp9_hip.h"
 
-#define SVT_CTX_SLOTS 57
+/* the context's grow-only device buffers (svt_ctx_slot).  0 .. 39 belong to the stages in front of the entropy coder (ME, transform,
+ * deblocking, MC, rate) and are numbered where they are used; the entropy side's are named here, one line a buffer, so that no two stages
+ * can pick the same one and a new stage adds a line in front of SVT_CTX_SLOTS */
+enum svt_ctx_slot_id {
+    SVT_SLOT_TOK_SCAN = 40,                                                                  /* tokenize.hip: the canonical scan array */
+    SVT_SLOT_TOK_QCOEFF, SVT_SLOT_TOK_BLOCKS, SVT_SLOT_TOK_TOKENS, SVT_SLOT_TOK_OFF, SVT_SLOT_TOK_COUNTS, /* svt_hip_tokenize_blocks' device twins */
+    SVT_SLOT_BC_SCRATCH, SVT_SLOT_BC_TABLES, SVT_SLOT_BC_IN, SVT_SLOT_BC_OUT,                /* boolcode.hip */
+    SVT_SLOT_MI_SB_OFF, SVT_SLOT_MI_TABLES,                                                  /* modeinfo.hip: per-SB offsets, probabilities */
+    SVT_SLOT_MII_SB_OFF, SVT_SLOT_MII_TABLES,                                                /* modeinfo_inter.hip: the same */
+    SVT_SLOT_MVR_PART,                                                                       /* mvrefs.hip: per-SB partial sums */
+    SVT_SLOT_MDI_PART, SVT_SLOT_MDI_LABEL,                                                   /* md_inter.hip: partial sums, the labelled records */
+    SVT_CTX_SLOTS
+};
 #define SVT_CTX_RING 64
 #define SVT_CTX_UPLOAD_RING 4   /* pinned staging buffers of svt_hip_mem_upload_2d_async */
 #define SVT_CTX_MARKERS 1024    /* completion markers in flight (svt_hip_ctx_marker_*) */

@@ -162,11 +162,10 @@ template <class S> int32_t syn_set_tables(svt_hip_ctx *ctx, const typename S::ta
 }
 
 template <class S> int32_t syn_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const typename S::picture *pics, int32_t width, int32_t height, int32_t mi_stride) {
-    if (!ctx || !pics || n_pics < 1 || n_pics > SYN_MAX_PICS || width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7) ||
-        mi_stride < (width >> 3))
-        return syn_error<S>(SVT_HIP_ERR_BAD_PARAMETER, "bad argument");
     syn_batch_dev<S> hb;
     memset(&hb, 0, sizeof hb);
+    if (!ctx || !pics || n_pics < 1 || n_pics > SYN_MAX_PICS || svt_tok_geom_of(width, height, mi_stride, &hb.g, &hb.sb_cols, &hb.n_sb))
+        return syn_error<S>(SVT_HIP_ERR_BAD_PARAMETER, "bad argument");
     for (int i = 0; i < n_pics; i++)
         if (const char *what = S::fill(pics[i], hb.pic[i])) return syn_error<S>(SVT_HIP_ERR_BAD_PARAMETER, what);
     if (!ctx->slot_bytes[S::TABLES_SLOT]) {
@@ -175,9 +174,6 @@ template <class S> int32_t syn_batch_device(svt_hip_ctx *ctx, int32_t n_pics, co
         return syn_error<S>(SVT_HIP_ERR_BAD_PARAMETER, what);
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    hb.g.mi_stride = mi_stride; hb.g.mi_rows = height >> 3; hb.g.mi_cols = width >> 3; hb.g.w4 = width >> 2; hb.g.h4 = height >> 2;
-    hb.sb_cols = (width + 63) >> 6;
-    hb.n_sb = hb.sb_cols * ((height + 63) >> 6);
     uint32_t *sb_off = (uint32_t *)svt_ctx_slot(ctx, S::SCRATCH_SLOT, sizeof(uint32_t) * (size_t)n_pics * ((size_t)hb.n_sb + 1));
     if (!sb_off) return syn_error<S>(SVT_HIP_ERR_NO_RESOURCES, "scratch");
     for (int i = 0; i < n_pics; i++) hb.pic[i].sb_off = sb_off + (size_t)i * ((size_t)hb.n_sb + 1);

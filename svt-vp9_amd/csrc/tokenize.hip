@@ -27,7 +27,6 @@
 #define TOK_MAX_PICS 32
 #define TOK_SB_RUN 8          /* SBs per workgroup of the emit kernel: 8 x 6144 tokens at most (< 65536) */
 #define TOK_BLOCK_RUN 64      /* blocks per workgroup of the block-level kernel: a bin receives at most 1003 tokens of a block (band 5 of a 32x32) */
-#define TOK_SCAN_SLOT 40
 #define TOK_SCAN_ENTRIES (4 * (50 + 194 + 770 + 3074))
 
 namespace {
@@ -214,17 +213,17 @@ __global__ __launch_bounds__(256) void svt_tok_blocks_kernel(const int16_t *__re
 
 /* the canonical scan array on the device: uploaded once per context */
 const int16_t *device_scan(svt_hip_ctx *ctx) {
-    const bool first = ctx->slot_bytes[TOK_SCAN_SLOT] == 0;
-    int16_t   *d = (int16_t *)svt_ctx_slot(ctx, TOK_SCAN_SLOT, sizeof(int16_t) * TOK_SCAN_ENTRIES);
+    const bool first = ctx->slot_bytes[SVT_SLOT_TOK_SCAN] == 0;
+    int16_t   *d = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_TOK_SCAN, sizeof(int16_t) * TOK_SCAN_ENTRIES);
     if (!d) return nullptr;
     if (first) {
         int32_t        entries = 0;
         const int16_t *h = svt_hip_vp9_scan_tables(nullptr, &entries);
         if (entries != TOK_SCAN_ENTRIES || hipMemcpyAsync(d, h, sizeof(int16_t) * TOK_SCAN_ENTRIES, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            ctx->slot_bytes[TOK_SCAN_SLOT] = 0; /* (the buffer stays; the next call uploads again) */
-            (void)hipFree(ctx->slot[TOK_SCAN_SLOT]);
-            ctx->slot[TOK_SCAN_SLOT] = nullptr;
+            ctx->slot_bytes[SVT_SLOT_TOK_SCAN] = 0; /* (the buffer stays; the next call uploads again) */
+            (void)hipFree(ctx->slot[SVT_SLOT_TOK_SCAN]);
+            ctx->slot[SVT_SLOT_TOK_SCAN] = nullptr;
             return nullptr;
         }
     }
@@ -234,8 +233,9 @@ const int16_t *device_scan(svt_hip_ctx *ctx) {
 } // namespace
 
 extern "C" int32_t svt_hip_tokenize_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_tok_picture *pics, int32_t width, int32_t height, int32_t mi_stride) {
-    if (!ctx || !pics || n_pics < 1 || n_pics > TOK_MAX_PICS || width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7) ||
-        mi_stride < (width >> 3))
+    tok_batch_dev hb;
+    memset(&hb, 0, sizeof hb);
+    if (!ctx || !pics || n_pics < 1 || n_pics > TOK_MAX_PICS || svt_tok_geom_of(width, height, mi_stride, &hb.g, &hb.sb_cols, &hb.n_sb))
         return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "tokenize: bad argument");
     for (int i = 0; i < n_pics; i++) {
         const svt_tok_picture &p = pics[i];
@@ -246,11 +246,6 @@ extern "C" int32_t svt_hip_tokenize_batch_device(svt_hip_ctx *ctx, int32_t n_pic
     HIP_TRY(hipSetDevice(ctx->device));
     const int16_t *d_scan = device_scan(ctx);
     if (!d_scan) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tokenize: scan tables");
-    tok_batch_dev hb;
-    memset(&hb, 0, sizeof hb);
-    hb.g.mi_stride = mi_stride; hb.g.mi_rows = height >> 3; hb.g.mi_cols = width >> 3; hb.g.w4 = width >> 2; hb.g.h4 = height >> 2;
-    hb.sb_cols = (width + 63) >> 6;
-    hb.n_sb = hb.sb_cols * ((height + 63) >> 6);
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     for (int i = 0; i < n_pics; i++) {
         const svt_tok_picture &p = pics[i];
@@ -303,11 +298,11 @@ extern "C" int32_t svt_hip_tokenize_blocks(svt_hip_ctx *ctx, const int16_t *qcoe
             return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "tokenize: bad block (scan_off must name a table of the canonical layout)");
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    int16_t        *dq = (int16_t *)svt_ctx_slot(ctx, 41, sizeof(int16_t) * coeff_count);
-    svt_rate_block *db = (svt_rate_block *)svt_ctx_slot(ctx, 42, sizeof(svt_rate_block) * (size_t)n_blocks);
-    uint32_t       *dt = (uint32_t *)svt_ctx_slot(ctx, 43, sizeof(uint32_t) * ((size_t)capacity + 1));
-    uint32_t       *doff = (uint32_t *)svt_ctx_slot(ctx, 44, sizeof(uint32_t) * ((size_t)n_blocks + 1));
-    uint32_t       *dc = (uint32_t *)svt_ctx_slot(ctx, 45, sizeof(uint32_t) * SVT_TOK_COUNTS);
+    int16_t        *dq = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_TOK_QCOEFF, sizeof(int16_t) * coeff_count);
+    svt_rate_block *db = (svt_rate_block *)svt_ctx_slot(ctx, SVT_SLOT_TOK_BLOCKS, sizeof(svt_rate_block) * (size_t)n_blocks);
+    uint32_t       *dt = (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_TOK_TOKENS, sizeof(uint32_t) * ((size_t)capacity + 1));
+    uint32_t       *doff = (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_TOK_OFF, sizeof(uint32_t) * ((size_t)n_blocks + 1));
+    uint32_t       *dc = (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_TOK_COUNTS, sizeof(uint32_t) * SVT_TOK_COUNTS);
     if (!dq || !db || !dt || !doff || !dc) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tokenize: device buffers");
     HIP_TRY(hipMemcpyAsync(dq, qcoeff, sizeof(int16_t) * coeff_count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(db, blocks, sizeof(svt_rate_block) * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->stream));

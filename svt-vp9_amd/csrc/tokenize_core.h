@@ -84,6 +84,15 @@ typedef struct svt_tok_geom {
 typedef struct svt_tok_block {
     int ts, tt, inter, eob, ctx;
 } svt_tok_block;
+/* the pictures every grid stage takes: width / height 8 .. 8192 and a multiple of 8, mi_stride >= mi_cols.  0 and the geometry, the SBs
+ * of a row and of the picture filled in; 1, nothing written, for any other picture */
+SVT_HD int svt_tok_geom_of(int width, int height, int mi_stride, svt_tok_geom *g, int *sb_cols, int *n_sb) {
+    if (width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7) || mi_stride < (width >> 3)) return 1;
+    g->mi_stride = mi_stride; g->mi_rows = height >> 3; g->mi_cols = width >> 3; g->w4 = width >> 2; g->h4 = height >> 2;
+    *sb_cols = (width + 63) >> 6;
+    *n_sb = *sb_cols * ((height + 63) >> 6);
+    return 0;
+}
 
 SVT_HD int svt_tok_map_offset(const svt_tok_geom *g, int plane) {
     return plane == 0 ? 0 : g->w4 * g->h4 + (plane == 2 ? (g->w4 >> 1) * (g->h4 >> 1) : 0);

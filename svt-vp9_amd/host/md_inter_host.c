@@ -13,24 +13,20 @@ static void bad_grid(const svt_md_inter_picture *pic) {
 }
 
 int32_t svt_hip_md_inter_modes_picture(const svt_md_inter_picture *pic, int32_t width, int32_t height, int32_t mi_stride) {
-    if (!pic || !pic->d_lf_mi || !pic->d_mc_mi || !pic->d_ext_out || !pic->d_status || width < 8 || height < 8 || width > 8192 || height > 8192 ||
-        (width & 7) || (height & 7) || mi_stride < (width >> 3) || (pic->ref_mask & 0xF1))
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
+    if (!pic || !pic->d_lf_mi || !pic->d_mc_mi || !pic->d_ext_out || !pic->d_status || svt_tok_geom_of(width, height, mi_stride, &g, &sb_cols, &n_sb) ||
+        (pic->ref_mask & 0xF1))
         return SVT_HIP_ERR_BAD_PARAMETER;
     const svt_mdi_frame m = svt_mdi_frame_of(pic);
     if (svt_mii_bad_frame(&m.f)) return SVT_HIP_ERR_BAD_PARAMETER;
-    const svt_tok_geom g = {mi_stride, height >> 3, width >> 3, width >> 2, height >> 2};
-    const int          sb_cols = (width + 63) >> 6, n_sb = sb_cols * ((height + 63) >> 6);
     if (m.bad) {
         bad_grid(pic);
         return SVT_HIP_OK;
     }
     svt_mi_inter_ext *label = (svt_mi_inter_ext *)calloc((size_t)g.mi_rows * (size_t)mi_stride, sizeof *label);
     if (!label) return SVT_HIP_ERR_NO_RESOURCES;
-    svt_mvr_view v;
-    memset(&v, 0, sizeof v);
-    v.mi = pic->d_lf_mi; v.mc = pic->d_mc_mi; v.ext = label;
-    v.ref_mask = pic->ref_mask; v.restrict_ref_mvs = pic->restrict_ref_mvs != 0;
-    for (int k = 0; k < 4; k++) v.sign_bias |= (uint8_t)((pic->ref_frame_sign_bias[k] != 0) << k);
+    const svt_mvr_view v = svt_mvr_view_of(pic->d_lf_mi, pic->d_mc_mi, label, pic->ref_mask, pic->restrict_ref_mvs, pic->ref_frame_sign_bias);
     uint32_t inter_leaves = 0, new_leaves = 0, unfaithful_leaves = 0;
     for (int pass = 0; pass < 2; pass++) {
         if (pass)
@@ -45,10 +41,10 @@ int32_t svt_hip_md_inter_modes_picture(const svt_md_inter_picture *pic, int32_t 
             const int sb_r = (sb / sb_cols) * 8, sb_c = (sb % sb_cols) * 8;
             uint32_t  win[SVT_MVR_WIN_WORDS];
             for (int i = 0; i < SVT_MVR_WIN * SVT_MVR_WIN; i++) {
-                const int     r = sb_r - 3 + i / SVT_MVR_WIN, c = sb_c - 3 + i % SVT_MVR_WIN;
-                svt_mvr_entry e = {0, 0, 0};
-                if (r >= 0 && c >= 0 && r < g.mi_rows && c < g.mi_cols) e = pass ? svt_mvr_pack(&v, &g, r, c) : svt_mdi_pack(&v, &m, &g, r, c);
-                win[3 * i] = e.mv0; win[3 * i + 1] = e.mv1; win[3 * i + 2] = e.meta;
+                int           r, c;
+                svt_mvr_entry e = svt_mvr_no_entry();
+                if (svt_mvr_window_unit(&g, sb_r, sb_c, i, &r, &c)) e = pass ? svt_mvr_pack(&v, &g, r, c) : svt_mdi_pack(&v, &m, &g, r, c);
+                svt_mvr_window_put(win, i, e);
             }
             for (int z = 0; z < 64; z++) {
                 int ur, uc;

@@ -8,23 +8,23 @@
 #include "../../include/svtvp9_hip.h"
 #include "../csrc/modeinfo_core.h"
 
-static int bad_geometry(int32_t width, int32_t height) { return width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7); }
-
 uint32_t svt_hip_modes_segments(int32_t width, int32_t height) {
-    if (bad_geometry(width, height)) return 0;
-    return (uint32_t)(((width + 63) >> 6) * ((height + 63) >> 6)) * 64u * 4u;
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
+    return svt_tok_geom_of(width, height, width >> 3, &g, &sb_cols, &n_sb) ? 0 : (uint32_t)n_sb * 64u * 4u;
 }
 uint32_t svt_hip_modes_bools_capacity(int32_t width, int32_t height) {
-    if (bad_geometry(width, height)) return 0;
-    return (uint32_t)((width >> 3) * (height >> 3)) * SVT_MI_UNIT_BOOLS;
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
+    return svt_tok_geom_of(width, height, width >> 3, &g, &sb_cols, &n_sb) ? 0 : (uint32_t)(g.mi_cols * g.mi_rows) * SVT_MI_UNIT_BOOLS;
 }
 
 int32_t svt_hip_modes_kf_picture(const svt_modes_tables *tables, const svt_modes_picture *pic, int32_t width, int32_t height, int32_t mi_stride) {
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
     if (!tables || !pic || !pic->d_lf_mi || !pic->d_eob_map || !pic->d_tok_off || !pic->d_segments || !pic->d_n_bools || (!pic->d_bools && pic->capacity) ||
-        bad_geometry(width, height) || mi_stride < (width >> 3))
+        svt_tok_geom_of(width, height, mi_stride, &g, &sb_cols, &n_sb))
         return SVT_HIP_ERR_BAD_PARAMETER;
-    const svt_tok_geom g = {mi_stride, height >> 3, width >> 3, width >> 2, height >> 2};
-    const int          sb_cols = (width + 63) >> 6, n_sb = sb_cols * ((height + 63) >> 6);
     memset(pic->d_segments, 0, sizeof(svt_bool_segment) * 256 * (size_t)n_sb);
     for (int r = 0; r < g.mi_rows; r++)
         for (int c = 0; c < g.mi_cols; c++)

@@ -8,24 +8,23 @@
 #include "../../include/svtvp9_hip.h"
 #include "../csrc/modeinfo_inter_core.h"
 
-static int bad_geometry(int32_t width, int32_t height) { return width < 8 || height < 8 || width > 8192 || height > 8192 || (width & 7) || (height & 7); }
-
 static int bad_frame(const svt_modes_inter_picture *p) {
     const svt_mii_frame f = svt_mii_frame_of(p);
     return svt_mii_bad_frame(&f);
 }
 
 uint32_t svt_hip_modes_inter_bools_capacity(int32_t width, int32_t height) {
-    if (bad_geometry(width, height)) return 0;
-    return (uint32_t)((width >> 3) * (height >> 3)) * SVT_MII_UNIT_BOOLS;
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
+    return svt_tok_geom_of(width, height, width >> 3, &g, &sb_cols, &n_sb) ? 0 : (uint32_t)(g.mi_cols * g.mi_rows) * SVT_MII_UNIT_BOOLS;
 }
 
 int32_t svt_hip_modes_inter_picture(const svt_modes_inter_tables *tables, const svt_modes_inter_picture *pic, int32_t width, int32_t height, int32_t mi_stride) {
+    svt_tok_geom g;
+    int          sb_cols, n_sb;
     if (!tables || !pic || !pic->d_lf_mi || !pic->d_mc_mi || !pic->d_ext || !pic->d_eob_map || !pic->d_tok_off || !pic->d_segments || !pic->d_n_bools ||
-        (!pic->d_bools && pic->capacity) || bad_geometry(width, height) || mi_stride < (width >> 3) || bad_frame(pic))
+        (!pic->d_bools && pic->capacity) || svt_tok_geom_of(width, height, mi_stride, &g, &sb_cols, &n_sb) || bad_frame(pic))
         return SVT_HIP_ERR_BAD_PARAMETER;
-    const svt_tok_geom g = {mi_stride, height >> 3, width >> 3, width >> 2, height >> 2};
-    const int          sb_cols = (width + 63) >> 6, n_sb = sb_cols * ((height + 63) >> 6);
     const svt_mii_view v = {pic->d_lf_mi, pic->d_mc_mi, pic->d_ext, svt_mii_frame_of(pic)};
     memset(pic->d_segments, 0, sizeof(svt_bool_segment) * 256 * (size_t)n_sb);
     for (int r = 0; r < g.mi_rows; r++)

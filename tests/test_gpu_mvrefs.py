@@ -2,7 +2,8 @@
 (tests/golden/mvrefs_reference.npz) and the host form (svt_hip_mvrefs_picture): every fixture picture singly, a batch whose pictures
 differ in restrict flag, sign biases and ref_mask, wider grids, the 8192x64 and int16-ceiling pictures, a picture of 289 SBs, the chain
 tokeniser -> MV references -> inter mode info -> bool coder without a host round trip against the reference's tile bytes, the same chain
-behind the mode-decision stand-in and the inter encode pass, malformed grids, optional outputs left out, entry-point refusals."""
+behind the mode-decision stand-in and the inter encode pass, malformed grids, optional outputs left out, entry-point refusals, outputs at
+the records' own alignment alone and beside aligned ones in one call."""
 import ctypes as C
 
 import numpy as np
@@ -288,3 +289,58 @@ def test_entry_point_refusals(ctx):
     torch.cuda.synchronize()
     got = b.result()
     assert (got["raw_ext"] == 0xA5).all() and (got["raw_cand"] == 0x5A).all() and got["status"] == (0x77777777, 0x77777777)          # nothing ran
+
+
+class OffsetOutputs:
+    """d_ext_out and d_cand of one tight picture `offset` bytes behind a 16-byte boundary, guard bytes before and behind them"""
+
+    def __init__(self, p, offset):
+        self.units, self.offset = (p["H"] // 8) * (p["W"] // 8), offset
+        self.ext = torch.full((offset + self.units * 12 + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.cand = torch.full((offset + self.units * 32 + GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+        self.status = MvBuffers(p["W"], p["H"])
+
+    def struct(self, grids, p, want_ext=True):
+        s = self.status.struct(grids, p)
+        s.d_ext_out, s.d_cand = self.ext.data_ptr() + self.offset if want_ext else None, self.cand.data_ptr() + self.offset
+        assert self.ext.data_ptr() % 16 == 0 and s.d_cand % 16 == self.offset
+        return s
+
+    def check(self, want, want_ext=True):
+        """want: the host form's result"""
+        eo, ca, o = self.ext.cpu().numpy(), self.cand.cpu().numpy(), self.offset
+        assert bytes(eo[o:-GUARD]) == want["ext_out"].tobytes() if want_ext else (eo == 0xA5).all()
+        assert bytes(ca[o:-GUARD]) == want["cand"].tobytes()
+        assert (eo[:o] == 0xA5).all() and (eo[-GUARD:] == 0xA5).all() and (ca[:o] == 0x5A).all() and (ca[-GUARD:] == 0x5A).all()
+        assert self.status.result()["status"] == want["status"]
+
+
+def test_outputs_at_their_own_alignment_only(ctx):
+    """d_ext_out at an address that is 2 modulo 4 and d_cand at one that is 2 modulo 16 (the records' own alignment): the 16-bit stores"""
+    p = M.fixture_picture("mix_136x136_d")
+    grids = upload_grids(p)
+    out = OffsetOutputs(p, 2)
+    s = out.struct(grids, p)
+    assert s.d_ext_out % 4 == 2 and s.d_cand % 16 == 2
+    torch.cuda.synchronize()
+    mvrefs_device(ctx, 136, 136, [s])
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    want = M.host_mvrefs(p)
+    assert want["rc"] == 0 and want["status"][1] > 0
+    out.check(want)
+
+
+def test_store_forms_mixed_in_one_batch(ctx):
+    """three pictures of one call: aligned outputs; both outputs at the records' own alignment; d_ext_out left out and d_cand at its own
+    alignment -- the store form is chosen per picture inside one launch"""
+    p = M.fixture_picture("edge_72x40_b")
+    grids = upload_grids(p)
+    cases = ((0, True), (2, True), (2, False))
+    outs = [OffsetOutputs(p, offset) for offset, _ in cases]
+    torch.cuda.synchronize()
+    mvrefs_device(ctx, 72, 40, [o.struct(grids, p, want_ext) for o, (_, want_ext) in zip(outs, cases)])
+    B.check(B.load().svt_hip_ctx_synchronize(ctx))
+    want = M.host_mvrefs(p)
+    assert want["rc"] == 0 and want["status"][1] > 0
+    for o, (_, want_ext) in zip(outs, cases):
+        o.check(want, want_ext)
