@@ -160,6 +160,7 @@ int svt_ctx_stage(svt_hip_ctx *c, size_t bytes, void **host, void **dev) {
     if (c->ring_used[s]) { if (hipEventSynchronize(c->ring_ev[s]) != hipSuccess) return -1; c->ring_used[s] = 0; }
     if (bytes > c->ring_bytes[s]) {
         if (c->ring_own[s]) { /* (an entry inside the slabs owns nothing) */
+            (void)hipStreamSynchronize(c->stream); /* (kernels behind the slot's last copy may still use its device twin) */
             if (c->ring_host[s]) (void)hipHostFree(c->ring_host[s]);
             if (c->ring_dev[s]) (void)hipFree(c->ring_dev[s]);
         }

@@ -330,14 +330,7 @@ extern "C" void svt_hip_boolcode_geometry(int32_t *bools_per_chunk, int32_t *chu
 }
 
 extern "C" int32_t svt_hip_boolcode_set_tables(svt_hip_ctx *ctx, const svt_bool_tables *tables) {
-    if (!ctx || !tables) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: null argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* (a call in flight may still read the tables) */
-    void *d = svt_ctx_slot(ctx, SVT_SLOT_BC_TABLES, sizeof(svt_bool_tables));
-    if (!d) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: tables");
-    HIP_TRY(hipMemcpyAsync(d, tables, sizeof(svt_bool_tables), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SVT_HIP_OK;
+    return svt_ctx_set_tables(ctx, SVT_SLOT_BC_TABLES, tables, sizeof(svt_bool_tables), "boolcode");
 }
 
 extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams) {
@@ -382,10 +375,10 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
     }
     void *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: descriptor buffers");
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     memcpy(h, &hb, sizeof hb);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
-    svt_ctx_stage_commit(ctx);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
     const bc_batch_dev    *dB = (const bc_batch_dev *)d;
     const svt_bool_tables *dT = (const svt_bool_tables *)ctx->slot[SVT_SLOT_BC_TABLES];
     const dim3             ns((unsigned)n_streams);
@@ -398,9 +391,7 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
     hipLaunchKernelGGL(svt_bc_clear_kernel, dim3((max_words + 1023) / 1024, n_streams), dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_code_kernel, dim3((max_chunks + 63) / 64, n_streams), dim3(64), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_carry_kernel, ns, dim3(256), 0, ctx->stream, dB);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 

@@ -226,14 +226,12 @@ __global__ __launch_bounds__(64) void svt_md_default_kernel(const ed_batch_dev *
                         &P.lf_mi[ur * B->mi_stride + uc]);
 }
 
-/* the batch's parameter block goes to the device through the context's descriptor ring; the slot is committed at once: every
- * consumer is enqueued on the same stream behind the copy, and a later re-use of the slot is a copy on that stream too */
+/* the batch's parameter block goes to the device through the context's descriptor ring */
 int stage_batch(svt_hip_ctx *ctx, const ed_batch_dev &hb, const ed_batch_dev **d_out) {
     void *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return -1;
     memcpy(h, &hb, sizeof hb);
-    if (hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return -1;
-    svt_ctx_stage_commit(ctx);
+    if (svt_ctx_stage_send(ctx, sizeof hb) != hipSuccess) return -1;
     *d_out = (const ed_batch_dev *)d;
     return 0;
 }
@@ -413,8 +411,7 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
         void *h = nullptr, *d = nullptr;
         if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec: descriptor buffers");
         memcpy(h, qt, sizeof qt);
-        HIP_TRY(hipMemcpyAsync(w->d_qtabs, h, sizeof qt, hipMemcpyHostToDevice, ctx->stream));
-        svt_ctx_stage_commit(ctx);
+        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
     }
 #define ED_STAGE(k) do { if (w->hook) w->hook(w->hook_user, (k)); } while (0)
     /* 1. inter prediction of the whole batch */
@@ -516,8 +513,7 @@ extern "C" int32_t svt_hip_encdec_intra_device(svt_hip_ctx *ctx, svt_encdec_work
         void *h = nullptr, *d = nullptr;
         if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec_intra: descriptor buffers");
         memcpy(h, qt, sizeof qt);
-        HIP_TRY(hipMemcpyAsync(w->d_qtabs, h, sizeof qt, hipMemcpyHostToDevice, ctx->stream));
-        svt_ctx_stage_commit(ctx);
+        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
     }
     ED_STAGE(SVT_ENCDEC_STAGE_TQ);
     HIP_TRY(hipMemsetAsync(p.d_eob_map, 0, (size_t)(width / 4) * (height / 4) * 3 / 2 * sizeof(uint16_t), ctx->stream));

@@ -124,12 +124,10 @@ extern "C" int32_t svt_hip_frame_batch_device(svt_hip_ctx *ctx, int32_t n_pics, 
     memset(hb, 0, sizeof *hb);
     memcpy(hb->pk, packets, sizeof(svt_frame_packet) * (size_t)n_pics);
     hb->arena = d_arena; hb->table = d_table; hb->arena_capacity = arena_capacity; hb->n_pics = n_pics;
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(fr_batch_dev), hipMemcpyHostToDevice, ctx->stream));
-    svt_ctx_stage_commit(ctx);
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(fr_batch_dev)));
     hipLaunchKernelGGL(svt_fr_assemble_kernel, dim3(FR_WGS, (unsigned)n_pics), dim3(FR_LANES), 0, ctx->stream, (const fr_batch_dev *)d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }

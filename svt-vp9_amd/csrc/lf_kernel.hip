@@ -635,16 +635,18 @@ static int32_t lf_launch(svt_hip_ctx *ctx, int n_pics, const svt_yuv_planes *d_r
     if (svt_ctx_stage(ctx, desc_bytes + cnt_words * 4, (void **)&h, (void **)&d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf: scratch");
     uint32_t *cnt = (uint32_t *)(d + desc_bytes);
     /* per-SB edge descriptors of all pictures (grow-only context buffer) */
-    uint32_t *edesc = (uint32_t *)svt_ctx_slot(ctx, 24, (size_t)n_pics * max_rows * max_cols * LF_DESC_WORDS * sizeof(uint32_t));
+    uint32_t *edesc = (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_LF_EDESC, (size_t)n_pics * max_rows * max_cols * LF_DESC_WORDS * sizeof(uint32_t));
     if (!edesc) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf: descriptor buffer");
     for (int i = 0; i < n_pics; i++) {
         h[i].planes = d_recon[i]; h[i].lfm = d_lfm[i]; h[i].lfm_stride = lfm_stride[i]; h[i].mi_rows = mi_rows[i]; h[i].mi_cols = mi_cols[i];
         h[i].y_only = y_only; h[i].progress = cnt + 4 + (size_t)i * max_rows;
         h[i].desc = edesc + (size_t)i * max_rows * max_cols * LF_DESC_WORDS;
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(lf_pic_dev) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
+    /* (the counters behind the descriptors in the device twin are written by this launch's memset and kernels only, all on ctx->stream) */
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(lf_pic_dev) * (size_t)n_pics));
     HIP_TRY(hipMemsetAsync(cnt, 0, cnt_words * 4, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     static const bool want_prof = getenv("SVT_HIP_LF_PROFILE") != nullptr;
     if (want_prof) { unsigned long long z[8] = {0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_lf_prof), z, sizeof z)); }
     hipLaunchKernelGGL(svt_lf_desc_kernel, dim3(n_pics * max_rows * max_cols), dim3(128), 0, ctx->stream, (const lf_pic_dev *)d, max_rows, max_cols, *thr);
@@ -656,8 +658,7 @@ static int32_t lf_launch(svt_hip_ctx *ctx, int n_pics, const svt_yuv_planes *d_r
      * its seam rows the moment they appear.  Inside the pipelined step the change is neutral (other kernels fill the device either way);
      * one GOP at a time gains 6 %. */
     hipLaunchKernelGGL(svt_lf_kernel, dim3(n_pics * max_rows), dim3(256), 0, ctx->stream, (const lf_pic_dev *)d, n_pics, cnt, max_rows, want_prof ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_TRY(timer.end());
     if (want_prof) {
         unsigned long long hp[8];
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -680,8 +681,6 @@ static int32_t lf_launch(svt_hip_ctx *ctx, int n_pics, const svt_yuv_planes *d_r
             }
         }
     }
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
     return SVT_HIP_OK;
 }
 
@@ -692,7 +691,7 @@ extern "C" int32_t svt_hip_lf_reserve(svt_hip_ctx *ctx, int32_t n_pics, int32_t 
     if (!ctx || n_pics < 1 || mi_rows < 1 || mi_cols < 1) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "lf_reserve: bad argument");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t rows = (size_t)(mi_rows + 7) / 8, cols = (size_t)(mi_cols + 7) / 8;
-    if (!svt_ctx_slot(ctx, 24, (size_t)n_pics * rows * cols * LF_DESC_WORDS * sizeof(uint32_t))) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf: descriptor buffer");
+    if (!svt_ctx_slot(ctx, SVT_SLOT_LF_EDESC, (size_t)n_pics * rows * cols * LF_DESC_WORDS * sizeof(uint32_t))) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf: descriptor buffer");
     return SVT_HIP_OK;
 }
 
@@ -719,8 +718,8 @@ extern "C" int32_t svt_hip_lf_frame(svt_hip_ctx *ctx, const svt_yuv_planes *reco
     const size_t yb = (size_t)recon->y_stride * H, cb = (size_t)recon->uv_stride * CH;
     const int    sb_rows = (mi_rows + 7) / 8;
     const size_t mb = sizeof(svt_lf_mask) * (size_t)sb_rows * lfm_stride;
-    uint8_t *dy = (uint8_t *)svt_ctx_slot(ctx, 20, yb + 64), *du = (uint8_t *)svt_ctx_slot(ctx, 21, cb + 64), *dv = (uint8_t *)svt_ctx_slot(ctx, 22, cb + 64);
-    svt_lf_mask *dm = (svt_lf_mask *)svt_ctx_slot(ctx, 23, mb);
+    uint8_t *dy = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_LF_Y, yb + 64), *du = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_LF_U, cb + 64), *dv = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_LF_V, cb + 64);
+    svt_lf_mask *dm = (svt_lf_mask *)svt_ctx_slot(ctx, SVT_SLOT_LF_MASK, mb);
     if (!dy || !du || !dv || !dm) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf: device buffers");
     HIP_TRY(hipMemcpyAsync(dy, recon->y, yb, hipMemcpyHostToDevice, ctx->stream));
     if (!y_only) {

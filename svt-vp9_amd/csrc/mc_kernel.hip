@@ -203,14 +203,12 @@ int mc_launch(svt_hip_ctx *ctx, int n_pics, const svt_mc_picture *pics) {
         h[i].mi = pics[i].d_mi; h[i].mi_stride = pics[i].mi_stride; h[i].mi_rows = pics[i].mi_rows; h[i].mi_cols = pics[i].mi_cols;
         h[i].ref[0] = pics[i].ref[0]; h[i].ref[1] = pics[i].ref[1]; h[i].pred = pics[i].pred; h[i].use_subpel = pics[i].use_subpel;
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(mc_pic_dev) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(mc_pic_dev) * (size_t)n_pics));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     const int xblocks = (max_cols + 31) / 32, total = xblocks * max_rows * n_pics, chunk = (total + 7) / 8;
     hipLaunchKernelGGL(svt_mc_kernel, dim3(chunk * 8), dim3(128), 0, ctx->stream, (const mc_pic_dev *)d, max_rows, xblocks, total, chunk);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 } // namespace
@@ -230,7 +228,7 @@ extern "C" int32_t svt_hip_inter_pred_frame(svt_hip_ctx *ctx, const svt_mc_mode_
     svt_mc_picture p;
     memset(&p, 0, sizeof p);
     const size_t mi_bytes = sizeof(svt_mc_mode_info) * (size_t)mi_rows * mi_stride;
-    void        *dmi      = svt_ctx_slot(ctx, 26, mi_bytes);
+    void        *dmi      = svt_ctx_slot(ctx, SVT_SLOT_MC_MI, mi_bytes);
     if (!dmi) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "mc: device buffers");
     HIP_TRY(hipMemcpyAsync(dmi, mi, mi_bytes, hipMemcpyHostToDevice, ctx->stream));
     p.d_mi = (const svt_mc_mode_info *)dmi; p.mi_stride = mi_stride; p.mi_rows = mi_rows; p.mi_cols = mi_cols; p.use_subpel = use_subpel;
@@ -239,8 +237,10 @@ extern "C" int32_t svt_hip_inter_pred_frame(svt_hip_ctx *ctx, const svt_mc_mode_
         if (!r.y || !r.u || !r.v || r.org_x < 80 || r.org_y < 80 || (r.org_x & 1) || (r.org_y & 1))
             return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "mc: reference planes need an even padding of at least 80 luma samples");
         const size_t ny = (size_t)r.y_stride * (H + 2 * r.org_y), nuv = (size_t)r.uv_stride * (H / 2 + r.org_y);
-        uint8_t *dy = (uint8_t *)svt_ctx_slot(ctx, 27 + 3 * l, ny + 64);
-        uint8_t *du = (uint8_t *)svt_ctx_slot(ctx, 28 + 3 * l, nuv + 64), *dv = (uint8_t *)svt_ctx_slot(ctx, 29 + 3 * l, nuv + 64);
+        static_assert(3 * (sizeof p.ref / sizeof p.ref[0]) == SVT_SLOT_MC_REF_N, "three planes of each of the picture's reference lists");
+        const int slot = SVT_SLOT_MC_REF + 3 * l;
+        uint8_t  *dy = (uint8_t *)svt_ctx_slot(ctx, slot, ny + 64);
+        uint8_t  *du = (uint8_t *)svt_ctx_slot(ctx, slot + 1, nuv + 64), *dv = (uint8_t *)svt_ctx_slot(ctx, slot + 2, nuv + 64);
         if (!dy || !du || !dv) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "mc: device buffers");
         HIP_TRY(hipMemcpyAsync(dy, r.y, ny, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(du, r.u, nuv, hipMemcpyHostToDevice, ctx->stream));
@@ -252,7 +252,7 @@ extern "C" int32_t svt_hip_inter_pred_frame(svt_hip_ctx *ctx, const svt_mc_mode_
     }
     /* prediction planes: one buffer, Y then U then V; units of non-inter blocks keep the caller's samples */
     const size_t ysz = (size_t)W * H, csz = ysz / 4;
-    uint8_t     *dp  = (uint8_t *)svt_ctx_slot(ctx, 33, ysz + 2 * csz);
+    uint8_t     *dp  = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_MC_PRED, ysz + 2 * csz);
     if (!dp) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "mc: device buffers");
     HIP_TRY(hipMemcpyAsync(dp, pred_y, ysz, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dp + ysz, pred_u, csz, hipMemcpyHostToDevice, ctx->stream));

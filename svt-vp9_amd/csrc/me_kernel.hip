@@ -231,13 +231,13 @@ static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture 
             if (band < 1 || Li.hme_tw0 > 256 || Li.hme_th0 > 256) fast_ok = false;
         }
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(me_pic_dev) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(me_pic_dev) * (size_t)n_pics));
     const int total = n_sb * n_pics, chunk = (n_sb + 7) / 8; /* SBs of one picture per XCD */
     /* SVT_HIP_ME_PROFILE=1: per-phase shader-cycle breakdown (thread 0 of every workgroup), printed to stderr */
     static const bool want_prof = getenv("SVT_HIP_ME_PROFILE") != nullptr;
     unsigned long long *d_prof = nullptr;
     if (want_prof) {
-        d_prof = (unsigned long long *)svt_ctx_slot(ctx, 25, 32 * sizeof(unsigned long long));
+        d_prof = (unsigned long long *)svt_ctx_slot(ctx, SVT_SLOT_ME_PROF, 32 * sizeof(unsigned long long));
         if (d_prof) HIP_TRY(hipMemsetAsync(d_prof, 0, 32 * sizeof(unsigned long long), ctx->stream));
     }
 #ifdef ME_FINE_PROF
@@ -253,11 +253,12 @@ static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture 
     uint32_t     *d_redo = nullptr;
     if (me_spec_has_compact(spec) && (params->search_area_width & 7) == 0 && params->search_area_width <= 127 && me_lds_layout_compute_ex(params, &Lc, 1) == 0 &&
         me_lds_workgroups_per_cu(&Lc) > me_lds_workgroups_per_cu(&L)) {
-        d_redo = (uint32_t *)svt_ctx_slot(ctx, 39, (size_t)total * sizeof(uint32_t));
+        d_redo = (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_ME_REDO, (size_t)total * sizeof(uint32_t));
         if (!d_redo) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "me: redo flags");
         HIP_TRY(hipMemsetAsync(d_redo, 0, (size_t)total * sizeof(uint32_t), ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     /* me_fast.h's driver where a compiled instance of it serves the parameter set (me_spec_fast; today SPEC 1) */
     const bool           fast = fast_ok && !no_fast && me_spec_fast(spec);
     const me_launch_args a = {ctx->stream, chunk * 8 * n_pics, d, params, n_sb, nx, W, H, total, chunk, d_prof};
@@ -270,8 +271,7 @@ static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture 
     default: HIP_TRY(me_dispatch_sb<0>(a, L, Lc, d_redo)); break;
     }
     ctx->me_instance = spec + (fast ? 100 : d_redo ? 200 : 0); /* (d_redo: me_dispatch_sb issued the compact layout's two launches) */
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_TRY(timer.end());
     if (d_prof) {
         unsigned long long hp[32];
         HIP_TRY(hipMemcpyAsync(hp, d_prof, sizeof hp, hipMemcpyDeviceToHost, ctx->stream));
@@ -289,8 +289,6 @@ static int32_t me_launch(svt_hip_ctx *ctx, int32_t n_pics, const svt_pa_picture 
                     100.0 * (double)hp[17] / (double)tot, 100.0 * (double)hp[18] / (double)tot, 100.0 * (double)hp[19] / (double)tot);
         fprintf(stderr, "\n");
     }
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
     return SVT_HIP_OK;
 }
 
@@ -353,13 +351,15 @@ extern "C" int32_t svt_hip_me_picture(svt_hip_ctx *ctx, const svt_pa_picture *cu
         if (!hp[i]) continue;
         const int need_q = params->enable_hme_level_1_flag, need_s = params->enable_hme_level_0_flag;
         *dp[i] = *hp[i];
-        if (upload_plane(ctx, &hp[i]->full, &dp[i]->full, 3 * i)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
-        if (need_q && upload_plane(ctx, &hp[i]->quarter, &dp[i]->quarter, 3 * i + 1)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
-        if (need_s && upload_plane(ctx, &hp[i]->sixteenth, &dp[i]->sixteenth, 3 * i + 2)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
+        static_assert(3 * (sizeof hp / sizeof hp[0]) == SVT_SLOT_ME_PLANES_N, "three planes of each of hp's pictures");
+        const int slot = SVT_SLOT_ME_PLANES + 3 * i;
+        if (upload_plane(ctx, &hp[i]->full, &dp[i]->full, slot)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
+        if (need_q && upload_plane(ctx, &hp[i]->quarter, &dp[i]->quarter, slot + 1)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
+        if (need_s && upload_plane(ctx, &hp[i]->sixteenth, &dp[i]->sixteenth, slot + 2)) return svt_set_error(SVT_HIP_ERR_DEVICE, "me: upload");
     }
     const int         n_sb = svt_hip_sb_count(cur->full.width, cur->full.height);
-    svt_me_pu_result *dr   = (svt_me_pu_result *)svt_ctx_slot(ctx, 9, sizeof(svt_me_pu_result) * 85 * (size_t)n_sb);
-    uint32_t         *drc  = rcme ? (uint32_t *)svt_ctx_slot(ctx, 10, sizeof(uint32_t) * (size_t)n_sb) : nullptr;
+    svt_me_pu_result *dr   = (svt_me_pu_result *)svt_ctx_slot(ctx, SVT_SLOT_ME_RESULTS, sizeof(svt_me_pu_result) * 85 * (size_t)n_sb);
+    uint32_t         *drc  = rcme ? (uint32_t *)svt_ctx_slot(ctx, SVT_SLOT_ME_RCME, sizeof(uint32_t) * (size_t)n_sb) : nullptr;
     if (!dr || (rcme && !drc)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "me: result buffers");
     int32_t rc = svt_hip_me_picture_device(ctx, &dc, &d0, ref1 ? &d1 : nullptr, params, dr, drc);
     if (rc) return rc;
@@ -399,12 +399,11 @@ extern "C" int32_t svt_hip_me_zz_sad_device(svt_hip_ctx *ctx, const svt_plane *c
     static const int th_shift[4] = {4, 2, 0, 0}; /* non_moving_th_shift, Codec/EbMotionEstimationProcess.c:353 */
     HIP_TRY(hipSetDevice(ctx->device));
     const int nx = (prev_input->width + ME_SB - 1) / ME_SB, ny = (prev_input->height + ME_SB - 1) / ME_SB, n_sb = nx * ny;
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_me_zz_sad_kernel, dim3((n_sb + 3) / 4), dim3(256), 0, ctx->stream, *cur_sixteenth, *prev_input, nx, n_sb,
                        th_shift[input_resolution], d_zz_sad, d_non_moving_index);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -413,11 +412,10 @@ extern "C" int32_t svt_hip_sad_loop_batch_device(svt_hip_ctx *ctx, const uint8_t
     if (!ctx || !d_src || !d_ref || !d_jobs || !d_out || n_jobs < 1) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "sad_loop: null argument");
     HIP_TRY(hipSetDevice(ctx->device));
     const int lds = 64 * 1024;
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_sad_loop_kernel, dim3(n_jobs), dim3(256), lds, ctx->stream, d_src, d_ref, d_jobs, n_jobs, d_out, lds);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -501,11 +499,10 @@ extern "C" int32_t svt_hip_me_sb_stats_device(svt_hip_ctx *ctx, const svt_me_sb_
         return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "sb_stats: histogram / rcme buffers missing");
     HIP_TRY(hipSetDevice(ctx->device));
     const int nx = (params->pic_width + ME_SB - 1) / ME_SB, ny = (params->pic_height + ME_SB - 1) / ME_SB, n_sb = nx * ny;
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_me_sb_stats_kernel, dim3((n_sb + 255) / 256), dim3(256), 0, ctx->stream, *params, nx, n_sb, d_results, d_var, d_rcme, d_stats,
                        d_hist, d_full_sb_count);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }

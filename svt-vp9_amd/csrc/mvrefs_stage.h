@@ -176,14 +176,12 @@ int32_t mvs_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const typename S::pic
     for (int i = 0; i < n_pics; i++) hb.pic[i].part = part + S::N * (size_t)i * (size_t)hb.n_sb;
     void *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return mvs_error<S>(SVT_HIP_ERR_NO_RESOURCES, "descriptor buffers");
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     memcpy(h, &hb, sizeof hb);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
-    svt_ctx_stage_commit(ctx);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
     launch((const mvs_batch_dev<S> *)d, hb.n_sb);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 #endif

@@ -128,11 +128,10 @@ extern "C" int32_t svt_hip_pa_mean_variance_device(svt_hip_ctx *ctx, const svt_p
     if (nx * 64 - full->width > full->origin_x || ny * 64 - full->height > full->origin_y)
         return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "pa: padding smaller than the partial SB");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_pa_meanvar_kernel, dim3((n_sb + 3) / 4), dim3(256), 0, ctx->stream, *full, nx, n_sb, d_mean, d_var);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -159,12 +158,10 @@ extern "C" int32_t svt_hip_pa_prepare_batch_device(svt_hip_ctx *ctx, int32_t n_p
             rows += (J.dh + 2 * J.pad_y + PA_ROWS - 1) / PA_ROWS;
         }
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(pa_job) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(pa_job) * (size_t)n_jobs));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_pa_plane_kernel, dim3(rows), dim3(256), 0, ctx->stream, (const pa_job *)d, n_jobs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }

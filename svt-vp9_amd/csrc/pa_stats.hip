@@ -396,7 +396,7 @@ extern "C" int32_t svt_hip_pa_noise_batch_device(svt_hip_ctx *ctx, int32_t n_pic
     size_t tiles_max = 0; /* the job records are followed, on the device side only, by one partial sum per tile */
     for (int i = 0; i < n_pics; i++) tiles_max += (size_t)((pics[i].full.width + 63) / 64) * (size_t)((pics[i].full.height + 63) / 64);
     const size_t jobs_b = (sizeof(ps_noise_job) * (size_t)n_pics + 7) & ~(size_t)7;
-    char *hb = nullptr, *db = nullptr;
+    char *hb = nullptr, *db = nullptr; /* (the partial sums are written and read by this call's kernels only, all on ctx->stream) */
     if (svt_ctx_stage(ctx, jobs_b + sizeof(uint32_t) * tiles_max, (void **)&hb, (void **)&db)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "pa noise: scratch");
     ps_noise_job *h = (ps_noise_job *)hb, *d = (ps_noise_job *)db;
     uint32_t     *d_part = (uint32_t *)(db + jobs_b);
@@ -423,18 +423,16 @@ extern "C" int32_t svt_hip_pa_noise_batch_device(svt_hip_ctx *ctx, int32_t n_pic
     }
     /* noise_detection_th selects NOISE_MIN_LEVEL(_DECIM)_0 / _1 (:32-37); the quarter form tests it the other way round (:3884-3888) */
     const uint32_t th = M == 2 ? (params->noise_detection_th == 0 ? 120000u : 70000u) : (params->noise_detection_th == 1 ? 70000u : 120000u);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(ps_noise_job) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(ps_noise_job) * (size_t)n_pics));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     if (M == 0) hipLaunchKernelGGL(svt_pa_noise_kernel<0>, dim3(tiles), dim3(256), 0, ctx->stream, (const ps_noise_job *)d, n_pics, th, d_part);
     else if (M == 1) hipLaunchKernelGGL(svt_pa_noise_kernel<1>, dim3(tiles), dim3(256), 0, ctx->stream, (const ps_noise_job *)d, n_pics, th, d_part);
     else hipLaunchKernelGGL(svt_pa_noise_kernel<2>, dim3(tiles), dim3(256), 0, ctx->stream, (const ps_noise_job *)d, n_pics, th, d_part);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(svt_pa_noise_class_kernel, dim3(n_pics), dim3(256), 0, ctx->stream, (const ps_noise_job *)d, (const uint32_t *)d_part, d_result, M,
                        params->luma_height);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -447,7 +445,8 @@ extern "C" int32_t svt_hip_pa_histogram_batch_device(svt_hip_ctx *ctx, int32_t n
     const int    n_reg = regions_w * regions_h;
     const size_t jobs_b = (sizeof(ps_hist_job) * (size_t)n_pics + 7) & ~(size_t)7, sums_b = sizeof(uint64_t) * (size_t)n_pics * n_reg * 3,
                  part_b = sizeof(uint64_t) * (size_t)n_pics * PS_MEAN_WGS;
-    char *h = nullptr, *d = nullptr; /* the job records, then (device side only) the region sums and the partial sums of the luma mean */
+    /* the job records, then (device side only) the region sums and the partial sums of the luma mean: this call's kernels write and read them, all on ctx->stream */
+    char *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, jobs_b + sums_b + part_b, (void **)&h, (void **)&d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "pa histogram: scratch");
     ps_hist_job *hj = (ps_hist_job *)h;
     for (int i = 0; i < n_pics; i++) {
@@ -466,8 +465,9 @@ extern "C" int32_t svt_hip_pa_histogram_batch_device(svt_hip_ctx *ctx, int32_t n
         J.w16 = y->width; J.h16 = y->height; J.W = W; J.H = H;
     }
     uint64_t *d_sums = (uint64_t *)(d + jobs_b), *d_part = (uint64_t *)(d + jobs_b + sums_b);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(ps_hist_job) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(ps_hist_job) * (size_t)n_pics));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_pa_hist_kernel, dim3(n_reg * 3, n_pics), dim3(256), 0, ctx->stream, (const ps_hist_job *)d, regions_w, regions_h, d_sums);
     HIP_TRY(hipGetLastError());
     if (scd_mode == 0) {
@@ -476,10 +476,7 @@ extern "C" int32_t svt_hip_pa_histogram_batch_device(svt_hip_ctx *ctx, int32_t n
     }
     hipLaunchKernelGGL(svt_pa_avg_kernel, dim3((n_pics + 63) / 64), dim3(64), 0, ctx->stream, (const ps_hist_job *)d, n_pics, n_reg, scd_mode,
                        (const uint64_t *)d_sums, (const uint64_t *)d_part);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -502,12 +499,10 @@ extern "C" int32_t svt_hip_pa_chroma_mean_batch_device(svt_hip_ctx *ctx, int32_t
         if (!d_cb_mean[i] || !d_cr_mean[i]) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "pa chroma mean: null output");
         h[i].out[0] = d_cb_mean[i]; h[i].out[1] = d_cr_mean[i];
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(ps_cmean_job) * (size_t)n_pics, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(ps_cmean_job) * (size_t)n_pics));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_pa_chroma_mean_kernel, dim3((n_sb + 3) / 4, n_pics), dim3(256), 0, ctx->stream, (const ps_cmean_job *)d, width, height, nx, n_sb);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }

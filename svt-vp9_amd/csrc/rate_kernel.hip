@@ -80,13 +80,12 @@ extern "C" int32_t svt_hip_coeff_rate_batch_device(svt_hip_ctx *ctx, const int16
     if (((uintptr_t)d_scan & 3) || ((uintptr_t)d_blocks & 15) || ((uintptr_t)d_qcoeff & 15))
         return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "rate: scan / block / coefficient arrays must be 4 / 16 / 16-byte aligned");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     const int dev_cus = ctx->cu_count;
     const int want = (n_blocks + 15) / 16, cap = dev_cus * 5; /* 31 KB of LDS per workgroup: five per CU */
     hipLaunchKernelGGL(svt_rate_kernel, dim3(want < cap ? want : cap), dim3(256), 0, ctx->stream, d_qcoeff, d_blocks, n_blocks, d_tables, d_scan, d_bits);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -100,13 +99,13 @@ extern "C" int32_t svt_hip_coeff_rate_batch(svt_hip_ctx *ctx, const int16_t *qco
             return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "rate: bad block");
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    int16_t          *dq = (int16_t *)svt_ctx_slot(ctx, 34, sizeof(int16_t) * coeff_count);
-    svt_rate_block   *db = (svt_rate_block *)svt_ctx_slot(ctx, 35, sizeof(svt_rate_block) * (size_t)n_blocks);
-    svt_rate_tables  *dt = (svt_rate_tables *)svt_ctx_slot(ctx, 36, sizeof(svt_rate_tables));
+    int16_t          *dq = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_RATE_QCOEFF, sizeof(int16_t) * coeff_count);
+    svt_rate_block   *db = (svt_rate_block *)svt_ctx_slot(ctx, SVT_SLOT_RATE_BLOCKS, sizeof(svt_rate_block) * (size_t)n_blocks);
+    svt_rate_tables  *dt = (svt_rate_tables *)svt_ctx_slot(ctx, SVT_SLOT_RATE_TABLES, sizeof(svt_rate_tables));
     /* the kernel's prologue copies the first RATE_SCAN_PREFETCH entries whatever the blocks use (see the header) */
     const size_t      scan_alloc = scan_count > RATE_SCAN_PREFETCH ? scan_count : RATE_SCAN_PREFETCH;
-    int16_t          *ds = (int16_t *)svt_ctx_slot(ctx, 37, sizeof(int16_t) * scan_alloc);
-    int32_t          *dbits = (int32_t *)svt_ctx_slot(ctx, 38, sizeof(int32_t) * (size_t)n_blocks);
+    int16_t          *ds = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_RATE_SCAN, sizeof(int16_t) * scan_alloc);
+    int32_t          *dbits = (int32_t *)svt_ctx_slot(ctx, SVT_SLOT_RATE_BITS, sizeof(int32_t) * (size_t)n_blocks);
     if (!dq || !db || !dt || !ds || !dbits) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "rate: device buffers");
     HIP_TRY(hipMemcpyAsync(dq, qcoeff, sizeof(int16_t) * coeff_count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(db, blocks, sizeof(svt_rate_block) * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->stream));

@@ -108,12 +108,10 @@ extern "C" int32_t svt_hip_ref_pad_batch_device(svt_hip_ctx *ctx, int32_t n_pics
             wgs += (J.h + 2 * J.pad_y + RP_ROWS - 1) / RP_ROWS;
         }
     }
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof(rp_job) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof(rp_job) * (size_t)n_jobs));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     hipLaunchKernelGGL(svt_refpad_kernel, dim3(wgs), dim3(256), 0, ctx->stream, (const rp_job *)d, n_jobs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    svt_ctx_stage_commit(ctx);
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }

@@ -3,14 +3,27 @@
 #define SVT_CTX_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 #include "../../include/svtvp9_hip.h"
 
-/* the context's grow-only device buffers (svt_ctx_slot).  0 .. 39 belong to the stages in front of the entropy coder (ME, transform,
- * deblocking, MC, rate) and are numbered where they are used; the entropy side's are named here, one line a buffer, so that no two stages
- * can pick the same one and a new stage adds a line in front of SVT_CTX_SLOTS */
+/* the context's grow-only device buffers (svt_ctx_slot): every buffer has a name here, one line a stage, so that no two stages can pick
+ * the same one; a new stage adds a line in front of SVT_CTX_SLOTS.  A family indexed by arithmetic is a base and its extent (_N), and the
+ * site that does the arithmetic checks it against the extent at compile time.  Nothing outside csrc sees the numbers. */
+enum { SVT_SLOT_ME_PLANES_N = 9, SVT_SLOT_MC_REF_N = 6 };
 enum svt_ctx_slot_id {
-    SVT_SLOT_TOK_SCAN = 40,                                                                  /* tokenize.hip: the canonical scan array */
+    SVT_SLOT_ME_PLANES,                                      /* svt_hip_me_picture: + 3 * picture (cur, ref0, ref1) + level (full, 1/4, 1/16) */
+    SVT_SLOT_ME_RESULTS = SVT_SLOT_ME_PLANES + SVT_SLOT_ME_PLANES_N, SVT_SLOT_ME_RCME,       /* svt_hip_me_picture's device twins */
+    SVT_SLOT_ME_PROF, SVT_SLOT_ME_REDO,                                                      /* me_launch: profile counters, redo flags */
+    SVT_SLOT_TQ_SRC, SVT_SLOT_TQ_PRED, SVT_SLOT_TQ_RECON, SVT_SLOT_TQ_BLOCKS, SVT_SLOT_TQ_QTABS, SVT_SLOT_TQ_ISCAN, SVT_SLOT_TQ_QCOEFF,
+    SVT_SLOT_TQ_DQCOEFF, SVT_SLOT_TQ_EOB,                                                    /* svt_hip_tq_batch's device twins */
+    SVT_SLOT_LF_Y, SVT_SLOT_LF_U, SVT_SLOT_LF_V, SVT_SLOT_LF_MASK,                           /* svt_hip_lf_frame's device twins */
+    SVT_SLOT_LF_EDESC,                                                                       /* lf_launch: edge descriptors */
+    SVT_SLOT_MC_MI, SVT_SLOT_MC_PRED,                                                        /* svt_hip_inter_pred_frame's device twins, and */
+    SVT_SLOT_MC_REF,                                                                         /* + 3 * list (0, 1) + plane (Y, Cb, Cr) */
+    SVT_SLOT_RATE_QCOEFF = SVT_SLOT_MC_REF + SVT_SLOT_MC_REF_N, SVT_SLOT_RATE_BLOCKS, SVT_SLOT_RATE_TABLES, SVT_SLOT_RATE_SCAN,
+    SVT_SLOT_RATE_BITS,                                                                      /* svt_hip_rate_batch's device twins */
+    SVT_SLOT_TOK_SCAN,                                                                       /* tokenize.hip: the canonical scan array */
     SVT_SLOT_TOK_QCOEFF, SVT_SLOT_TOK_BLOCKS, SVT_SLOT_TOK_TOKENS, SVT_SLOT_TOK_OFF, SVT_SLOT_TOK_COUNTS, /* svt_hip_tokenize_blocks' device twins */
     SVT_SLOT_BC_SCRATCH, SVT_SLOT_BC_TABLES, SVT_SLOT_BC_IN, SVT_SLOT_BC_OUT,                /* boolcode.hip */
     SVT_SLOT_MI_SB_OFF, SVT_SLOT_MI_TABLES,                                                  /* modeinfo.hip: per-SB offsets, probabilities */
@@ -32,8 +45,8 @@ struct svt_hip_ctx {
     int         cu_count;  /* compute units of the device (queried once at creation) */
     int         me_instance; /* kernel instance of the last ME launch: me_spec.h index, + 100 for me_fast.h's driver, + 200 for the two launches of the compact layout (me_layout.h) */
     int         intra_wgs;   /* svt_hip_ctx_set_intra_workgroups: 64-lane workers of the intra pass launched on this context (0 = default) */
-    /* ring of staging slots (pinned host + device twin) for launch descriptors: a slot is reused only after the
-       event recorded behind its last consumer has completed, so launches never synchronise the stream */
+    /* ring of staging slots (pinned host + device twin) for launch descriptors: a slot is reused only after the event
+       recorded behind its host-to-device copy has completed (svt_ctx_stage_send), so launches never synchronise the stream */
     void       *ring_host[SVT_CTX_RING];
     void       *ring_dev[SVT_CTX_RING];
     size_t      ring_bytes[SVT_CTX_RING];
@@ -66,11 +79,25 @@ struct svt_hip_ctx {
 
 int32_t svt_set_error(int32_t code, const char *msg);
 int32_t svt_set_hip_error(hipError_t e, const char *file, int line);
-/* next staging slot with at least `bytes` in both twins; returns 0 on success */
-int     svt_ctx_stage(svt_hip_ctx *ctx, size_t bytes, void **host, void **dev);
-/* call after the last operation that reads the slot has been enqueued on ctx->stream */
-void    svt_ctx_stage_commit(svt_hip_ctx *ctx);
-void   *svt_ctx_slot(svt_hip_ctx *ctx, int slot, size_t bytes);
+/* A launch descriptor goes to the device in two steps.  svt_ctx_stage takes the next staging slot with at least `bytes` in both twins
+ * (0 on success); the caller fills the host twin and may still return: nothing is in flight.  svt_ctx_stage_send copies the first `n`
+ * bytes of the host twin to `dst` (null: the slot's device twin) on ctx->stream and commits the slot in the same call; after it the
+ * caller owes the ring nothing on any path, and when the copy fails nothing is in flight and the slot is not committed.
+ * The commit's event sits right behind the copy, and that is enough: a context has exactly one stream, so every kernel that reads or
+ * writes the device twin is enqueued on it behind the copy, and a later use of the slot starts with a copy on that same stream, behind
+ * those kernels.  The event only keeps the host from rewriting the host twin while the copy is in flight.
+ * svt_ctx_stage_commit (record the slot's event, move on to the next slot) is the primitive behind svt_ctx_stage_send and nothing
+ * else calls it; until it has run, svt_ctx_stage answers with the same slot. */
+int   svt_ctx_stage(svt_hip_ctx *ctx, size_t bytes, void **host, void **dev);
+void  svt_ctx_stage_commit(svt_hip_ctx *ctx);
+void *svt_ctx_slot(svt_hip_ctx *ctx, int slot, size_t bytes);
+inline hipError_t svt_ctx_stage_send(svt_hip_ctx *ctx, size_t n, void *dst = nullptr) {
+    void *h = nullptr, *d = nullptr;
+    if (svt_ctx_stage(ctx, n, &h, &d)) return (hipError_t)1; /* hipErrorInvalidValue: no slot of n bytes had been taken */
+    const hipError_t e = hipMemcpyAsync(dst ? dst : d, h, n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) svt_ctx_stage_commit(ctx);
+    return e;
+}
 
 /* transform stage over device-built block lists (tq_kernel.hip; used by encdec.hip) */
 int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set,
@@ -89,4 +116,42 @@ int32_t svt_md_intra_default_launch(svt_hip_ctx *ctx, svt_lf_mode_info *d_lf_mi,
         hipError_t e_ = (expr);                                              \
         if (e_ != hipSuccess) return svt_set_hip_error(e_, __FILE__, __LINE__); \
     } while (0)
+
+/* the bracket behind svt_hip_last_kernel_ms: begin() records ev_start, end() checks the launches and records ev_stop.  A return in
+ * between closes the bracket from the destructor, so ev_start and ev_stop are always a pair of one call; `timed` changes only in end() */
+struct svt_ctx_timer {
+    svt_hip_ctx *ctx;
+    bool         open;
+    explicit svt_ctx_timer(svt_hip_ctx *c) : ctx(c), open(false) {}
+    svt_ctx_timer(const svt_ctx_timer &) = delete;
+    svt_ctx_timer &operator=(const svt_ctx_timer &) = delete;
+    ~svt_ctx_timer() { if (open) (void)hipEventRecord(ctx->ev_stop, ctx->stream); }
+    hipError_t begin() {
+        const hipError_t e = hipEventRecord(ctx->ev_start, ctx->stream);
+        open = e == hipSuccess;
+        return e;
+    }
+    hipError_t end() {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e != hipSuccess) return e; /* (the destructor tries ev_stop once more) */
+        open = false;
+        ctx->timed = 1;
+        return hipSuccess;
+    }
+};
+
+/* replace the constant tables a stage keeps in a grow-only buffer; `name` is the stage's error prefix */
+inline int32_t svt_ctx_set_tables(svt_hip_ctx *ctx, int slot, const void *tables, size_t bytes, const char *name) {
+    char msg[64];
+    snprintf(msg, sizeof msg, "%s: %s", name, ctx && tables ? "tables" : "null argument");
+    if (!ctx || !tables) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, msg);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* (a call in flight may still read the tables) */
+    void *d = svt_ctx_slot(ctx, slot, bytes);
+    if (!d) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, msg);
+    HIP_TRY(hipMemcpyAsync(d, tables, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SVT_HIP_OK;
+}
 #endif

@@ -151,14 +151,7 @@ template <class S> const char *syn_fill_common(const typename S::picture &p, syn
 }
 
 template <class S> int32_t syn_set_tables(svt_hip_ctx *ctx, const typename S::tables *tables) {
-    if (!ctx || !tables) return syn_error<S>(SVT_HIP_ERR_BAD_PARAMETER, "null argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* (a call in flight may still read the tables) */
-    void *d = svt_ctx_slot(ctx, S::TABLES_SLOT, sizeof(typename S::tables));
-    if (!d) return syn_error<S>(SVT_HIP_ERR_NO_RESOURCES, "tables");
-    HIP_TRY(hipMemcpyAsync(d, tables, sizeof(typename S::tables), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SVT_HIP_OK;
+    return svt_ctx_set_tables(ctx, S::TABLES_SLOT, tables, sizeof(typename S::tables), S::NAME);
 }
 
 template <class S> int32_t syn_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const typename S::picture *pics, int32_t width, int32_t height, int32_t mi_stride) {
@@ -179,18 +172,16 @@ template <class S> int32_t syn_batch_device(svt_hip_ctx *ctx, int32_t n_pics, co
     for (int i = 0; i < n_pics; i++) hb.pic[i].sb_off = sb_off + (size_t)i * ((size_t)hb.n_sb + 1);
     void *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return syn_error<S>(SVT_HIP_ERR_NO_RESOURCES, "descriptor buffers");
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     memcpy(h, &hb, sizeof hb);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
-    svt_ctx_stage_commit(ctx);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
     const syn_batch_dev<S>   *dB = (const syn_batch_dev<S> *)d;
     const typename S::tables *dT = (const typename S::tables *)ctx->slot[S::TABLES_SLOT];
     hipLaunchKernelGGL(syn_count_kernel<S>, dim3(n_pics * hb.n_sb), dim3(64), 0, ctx->stream, dB);
     hipLaunchKernelGGL(syn_scan_kernel<S>, dim3(n_pics), dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(syn_emit_kernel<S>, dim3((hb.n_sb + S::EMIT_WAVES - 1) / S::EMIT_WAVES, n_pics), dim3(64 * S::EMIT_WAVES), 0, ctx->stream, dB, dT);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 #endif

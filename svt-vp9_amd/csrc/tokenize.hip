@@ -246,7 +246,8 @@ extern "C" int32_t svt_hip_tokenize_batch_device(svt_hip_ctx *ctx, int32_t n_pic
     HIP_TRY(hipSetDevice(ctx->device));
     const int16_t *d_scan = device_scan(ctx);
     if (!d_scan) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tokenize: scan tables");
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     for (int i = 0; i < n_pics; i++) {
         const svt_tok_picture &p = pics[i];
         tok_pic_dev &P = hb.pic[i];
@@ -257,15 +258,12 @@ extern "C" int32_t svt_hip_tokenize_batch_device(svt_hip_ctx *ctx, int32_t n_pic
     void *h = nullptr, *d = nullptr;
     if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tokenize: descriptor buffers");
     memcpy(h, &hb, sizeof hb);
-    HIP_TRY(hipMemcpyAsync(d, h, sizeof hb, hipMemcpyHostToDevice, ctx->stream));
-    svt_ctx_stage_commit(ctx);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
     const tok_batch_dev *dB = (const tok_batch_dev *)d;
     hipLaunchKernelGGL(svt_tok_count_kernel, dim3(n_pics * hb.n_sb), dim3(64), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_tok_scan_kernel, dim3(n_pics), dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_tok_emit_kernel, dim3((hb.n_sb + TOK_SB_RUN - 1) / TOK_SB_RUN, n_pics), dim3(256), 0, ctx->stream, dB, d_scan);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 
@@ -276,14 +274,13 @@ extern "C" int32_t svt_hip_tokenize_blocks_device(svt_hip_ctx *ctx, const int16_
     HIP_TRY(hipSetDevice(ctx->device));
     const int16_t *d_scan = device_scan(ctx);
     if (!d_scan) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tokenize: scan tables");
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, SVT_TOK_COUNTS * sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(svt_tok_block_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_blocks, n_blocks, d_tok_off);
     hipLaunchKernelGGL(svt_tok_blocks_kernel, dim3((n_blocks + TOK_BLOCK_RUN - 1) / TOK_BLOCK_RUN), dim3(256), 0, ctx->stream, d_qcoeff, d_blocks, n_blocks, d_scan,
                        (const uint32_t *)d_tok_off, d_tokens, capacity, d_counts);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-    ctx->timed = 1;
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 

@@ -521,21 +521,26 @@ hipError_t launch_tq(svt_hip_ctx *ctx, const uint8_t *src, const uint8_t *pred, 
     }
 }
 
+/* several reconstruction buffers: their base pointers go to the device through the descriptor ring */
+int32_t tq_stage_recon_set(svt_hip_ctx *ctx, uint8_t *const *recon_set, int n_set, const uint8_t *const **d_set) {
+    void *h = nullptr, *d = nullptr;
+    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
+    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr; /* a block that names a set >= n_set is not reconstructed anywhere */
+    HIP_TRY(svt_ctx_stage_send(ctx, 8 * sizeof(void *)));
+    *d_set = (const uint8_t *const *)d;
+    return SVT_HIP_OK;
+}
+
 template <bool RATE>
 int32_t tq_launch_all(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_pred, uint8_t *d_recon, const svt_tq_block *d_blocks,
                       const int32_t size_count[4], const svt_quant_tables *d_qtabs, const int16_t *d_iscan, int16_t *d_qcoeff,
                       int16_t *d_dqcoeff, uint16_t *d_eob, uint64_t *d_dist, tq_rate_args ra, uint8_t *const *recon_set = nullptr, int n_set = 0) {
     HIP_TRY(hipSetDevice(ctx->device));
-    /* several reconstruction buffers: their base pointers go to the device through the descriptor ring */
     const uint8_t *const *d_set = nullptr;
-    if (recon_set) {
-        void *h = nullptr, *d = nullptr;
-        if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
-        for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr; /* a block that names a set >= n_set is not reconstructed anywhere */
-        HIP_TRY(hipMemcpyAsync(d, h, 8 * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-        d_set = (const uint8_t *const *)d;
-    }
-    HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+    if (recon_set)
+        if (const int32_t e = tq_stage_recon_set(ctx, recon_set, n_set, &d_set)) return e;
+    svt_ctx_timer timer(ctx);
+    HIP_TRY(timer.begin());
     int        off = 0;
     hipError_t rc = hipSuccess;
     auto at = [&](int o) { tq_rate_args r = ra; if (r.bits) r.bits += o; return r; };
@@ -546,10 +551,8 @@ int32_t tq_launch_all(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_p
     if (rc == hipSuccess) rc = launch_tq<16, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[2], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
     off += size_count[2];
     if (rc == hipSuccess) rc = launch_tq<32, RATE>(ctx, d_src, d_pred, d_recon, d_blocks + off, size_count[3], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob + off, d_dist ? d_dist + 2 * off : nullptr, at(off), d_set);
-    (void)hipEventRecord(ctx->ev_stop, ctx->stream); /* also on a failed launch: ev_start is already in the stream */
-    if (recon_set) svt_ctx_stage_commit(ctx);
-    if (rc != hipSuccess) return svt_set_hip_error(rc, __FILE__, __LINE__);
-    ctx->timed = 1;
+    HIP_TRY(rc);
+    HIP_TRY(timer.end());
     return SVT_HIP_OK;
 }
 } // namespace
@@ -563,11 +566,8 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
                                    const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, uint64_t *d_dist,
                                    const uint32_t *d_pos, const void *d_geom, int geom_stride, const uint32_t *d_iscan_off, int sb_cols) {
     HIP_TRY(hipSetDevice(ctx->device));
-    void *h = nullptr, *d = nullptr;
-    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
-    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr; /* a block that names a set >= n_set is not reconstructed anywhere */
-    HIP_TRY(hipMemcpyAsync(d, h, 8 * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t *const *d_set = (const uint8_t *const *)d;
+    const uint8_t *const *d_set = nullptr;
+    if (const int32_t e = tq_stage_recon_set(ctx, recon_set, n_set, &d_set)) return e;
     const tq_rate_args none = {nullptr, nullptr, nullptr};
     hipError_t rc = hipSuccess;
 #define TQ_DEV(N, S, D) launch_tq<N, false, D>(ctx, d_src, d_pred, nullptr, d_blocks, cap[S], d_qtabs, d_iscan, d_qcoeff, d_dqcoeff, d_eob, d_dist, none, d_set, tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols}, TQ_PER_2CU_ENC[S])
@@ -583,8 +583,7 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
         if (rc == hipSuccess) rc = TQ_DEV(32, 3, false);
     }
 #undef TQ_DEV
-    svt_ctx_stage_commit(ctx);
-    if (rc != hipSuccess) return svt_set_hip_error(rc, __FILE__, __LINE__);
+    HIP_TRY(rc);
     return SVT_HIP_OK;
 }
 
@@ -673,13 +672,13 @@ extern "C" int32_t svt_hip_tq_batch(svt_hip_ctx *ctx, const uint8_t *src, const 
         cnt[blocks[i].tx_size]++;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    uint8_t *ds = (uint8_t *)svt_ctx_slot(ctx, 11, plane_bytes + 64), *dp = (uint8_t *)svt_ctx_slot(ctx, 12, plane_bytes + 64);
-    uint8_t *dr = (uint8_t *)svt_ctx_slot(ctx, 13, plane_bytes + 64);
-    svt_tq_block *db = (svt_tq_block *)svt_ctx_slot(ctx, 14, sizeof(svt_tq_block) * (size_t)n_blocks);
-    svt_quant_tables *dqt = (svt_quant_tables *)svt_ctx_slot(ctx, 15, sizeof(svt_quant_tables) * (size_t)n_qtabs);
-    int16_t *dis = (int16_t *)svt_ctx_slot(ctx, 16, sizeof(int16_t) * iscan_count);
-    int16_t *dq = (int16_t *)svt_ctx_slot(ctx, 17, sizeof(int16_t) * coeff_count), *ddq = (int16_t *)svt_ctx_slot(ctx, 18, sizeof(int16_t) * coeff_count);
-    uint16_t *de = (uint16_t *)svt_ctx_slot(ctx, 19, sizeof(uint16_t) * (size_t)n_blocks);
+    uint8_t *ds = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_SRC, plane_bytes + 64), *dp = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_PRED, plane_bytes + 64);
+    uint8_t *dr = (uint8_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_RECON, plane_bytes + 64);
+    svt_tq_block *db = (svt_tq_block *)svt_ctx_slot(ctx, SVT_SLOT_TQ_BLOCKS, sizeof(svt_tq_block) * (size_t)n_blocks);
+    svt_quant_tables *dqt = (svt_quant_tables *)svt_ctx_slot(ctx, SVT_SLOT_TQ_QTABS, sizeof(svt_quant_tables) * (size_t)n_qtabs);
+    int16_t *dis = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_ISCAN, sizeof(int16_t) * iscan_count);
+    int16_t *dq = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_QCOEFF, sizeof(int16_t) * coeff_count), *ddq = (int16_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_DQCOEFF, sizeof(int16_t) * coeff_count);
+    uint16_t *de = (uint16_t *)svt_ctx_slot(ctx, SVT_SLOT_TQ_EOB, sizeof(uint16_t) * (size_t)n_blocks);
     if (!ds || !dp || !dr || !db || !dqt || !dis || !dq || !ddq || !de) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: device buffers");
     HIP_TRY(hipMemcpyAsync(ds, src, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dp, pred, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
