@@ -546,6 +546,20 @@ int32_t svt_hip_tq_batch(svt_hip_ctx *ctx, const uint8_t *src, const uint8_t *pr
                          const svt_quant_tables *qtabs, int32_t n_qtabs, const int16_t *iscan, size_t iscan_count,
                          int16_t *qcoeff, int16_t *dqcoeff, size_t coeff_count, uint16_t *eob);
 
+/* The decoder's half of the transform stage: quantised coefficients -> dequantise (DC dequant[0], AC dequant[1], the product kept in 16
+ * bits as the encode pass and a non-high-bit-depth decoder keep it; 32x32: product / 2 towards zero) -> inverse DCT / ADST with the
+ * eob shortcuts of VPX/vp9_idct.c:111-189 -> recon = clip(pred + residual); a block with eob 0 copies the prediction.
+ * d_blocks / size_count: svt_hip_tq_batch_device's lists (grouped by size); of a descriptor pred_off / pred_stride, recon_off /
+ * recon_stride, coeff_off, tx_type (ADST up to 16x16) and qtab are used, src_*, iscan_off, partial32 and do_recon are ignored (every
+ * block is reconstructed).  d_qcoeff (16-byte aligned) and d_eob (per list entry) are INPUTS -- what svt_hip_tq_batch_device wrote, or
+ * what a frame reader returned.  For such input d_recon receives exactly the bytes svt_hip_tq_batch_device's do_recon writes.
+ * d_overflow (may be NULL): set to the number of coefficients, over the blocks with eob != 0, whose dequantised value (after the
+ * division for 32x32) does not fit in 16 signed bits -- a conformant stream has none; the wrapped value is what gets used.
+ * Asynchronous on the context's stream. */
+int32_t svt_hip_recon_batch_device(svt_hip_ctx *ctx, const uint8_t *d_pred, uint8_t *d_recon, const svt_tq_block *d_blocks,
+                                   const int32_t size_count[4], const svt_quant_tables *d_qtabs, const int16_t *d_qcoeff,
+                                   const uint16_t *d_eob, uint32_t *d_overflow);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* In-loop deblocking                                                                                 */
 /* ------------------------------------------------------------------------------------------------ */
@@ -1240,6 +1254,22 @@ void    svt_hip_encdec_work_destroy(svt_hip_ctx *ctx, svt_encdec_work *work);
 int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work *work, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
                                     int32_t height, int32_t mi_stride, int32_t q_index, const svt_encdec_flags *flags,
                                     const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y);
+/* The decode pass: n_pics INTER pictures rebuilt from their coefficients and mode info -- what a decoder does with a parsed frame, on
+ * the workspace and picture records of svt_hip_encdec_batch_device.  Of a picture, src and d_dqcoeff are ignored; d_mc_mi, d_lf_mi
+ * (with `skip`), d_qcoeff (zero wherever nothing was coded) and d_eob_map are INPUTS; pred, recon, d_lfm and the grid's `skip` are
+ * written (d_nz is scratch).  Stages, asynchronous on the context's stream with no host round trip: inter prediction -> transform
+ * blocks from the grids -> svt_hip_recon_batch_device's arithmetic over them, each block's eob read from the eob map -> skip flags
+ * as a decoder derives them for the loop filter (an inter leaf of 8x8 or larger whose eobs are all zero is skipped) -> thr != NULL
+ * (the header's filter level is not 0): masks + deblocking -> border of pad_x / pad_y samples for every picture without no_pad.
+ * For the grids, coefficients and eob maps an encode pass left (do_recon, and apply_loop_filter / pad_reference as here) the planes, the
+ * masks and the skip flags equal that pass's byte for byte.
+ * d_status (device, required): d_status[0] = the number of coefficients whose dequantised value overflowed 16 bits (0 for a
+ * conformant stream).  A picture with has_intra is refused (SVT_HIP_ERR_UNSUPPORTED) before anything is launched; a grid that holds an
+ * is_inter = 0 leaf all the same, or is malformed, is reported by svt_hip_encdec_work_status, its blocks left out.  Intra blocks need a
+ * coefficient-driven form of the wavefront kernel. */
+int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work *work, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                    int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
+                                    int32_t *d_status);
 /* The encode pass of an INTRA picture (key frames, intra-refresh pictures): reference samples + the ten VP9 intra predictors +
  * transform / quantisation / reconstruction of every block in coding-dependency order (encode_pass_sb with intra blocks,
  * Codec/EbEncDecProcess.c:3680-4160: generate_intra_reference_samples :1128, intra_prediction Codec/EbIntraPrediction.c:16 ->
@@ -1443,6 +1473,95 @@ typedef struct svt_frame_params {
 int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes, uint32_t *compressed_bytes);
 /* the one-byte frame that shows DPB slot dpb_slot (0 .. 7): eb_vp9_pack_bitstream with show_existing_frame set */
 int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out);
+
+/* The header half of the frame reader (host/frame_read.c): the two headers parsed the way a decoder reads them (VP9 specification 6.2,
+ * 6.3), so that what the writers above produce is proven readable and not only equal to the reference's bytes.
+ * info->params: every coded field.  last_ref_deltas / last_mode_deltas are INPUTS (the stream's state in front of the frame), copied into
+ * params.last_*; a delta that is not sent keeps that value.  A field the frame does not code reads 0, except what a decoder infers:
+ * refresh_frame_mask 0xFF on a key frame; refresh_frame_context 0 and frame_parallel_decoding_mode 1 under error_resilient_mode; the
+ * render size = the frame size when none is sent; allow_comp_inter_inter = "the sign bias of GOLDEN or ALTREF differs from LAST's" (the
+ * decoder's condition for reading the reference-mode bits -- a writer that sends them under any other condition is misread);
+ * reference_mode from those bits, SINGLE without them.
+ * interp_filter is the filter AFTER the decoder's literal table {smooth, regular, sharp, bilinear}; tx_mode 0 ONLY_4X4 .. 3 ALLOW_32X32;
+ * needs_backward_adaptation = !error_resilient_mode && !frame_parallel_decoding_mode (a decoder then adapts its probabilities after the
+ * frame and leaves the fixed tables the entropy stages code with); lossless = q index 0 with all three delta qs 0.
+ * uncompressed_bytes / compressed_bytes (= first_part_size): the tile starts at their sum.  A show-existing frame sets
+ * show_existing_frame and show_existing_slot and nothing else (uncompressed_bytes 1).
+ * SVT_HIP_ERR_UNSUPPORTED with a message in svt_hip_last_error, for syntax the writers never produce: profile above 0, found_ref,
+ * a switchable filter is REPORTED (interp_filter) and not refused here, segmentation, more than one tile, TX_MODE_SELECT, any probability
+ * update flag of the compressed header.  `lossless` is REPORTED too: a decoder then reads no tx_mode and runs the Walsh-Hadamard transform, the
+ * writers send tx_mode all the same, so the bytes are parsed as written and a caller must not read a tile under that flag.
+ * SVT_HIP_ERR_BAD_PARAMETER for bytes that are no VP9 frame: wrong marker or sync code, a header that ends early, first_part_size 0 or
+ * beyond the frame, a set marker bit, a compressed header that ends inside a symbol.  Never reads at or beyond frame + size. */
+#define SVT_READ_FILTER_REGULAR 0     /* EIGHTTAP: the 8-tap kernel svt_mc_kernel implements */
+#define SVT_READ_FILTER_SMOOTH 1
+#define SVT_READ_FILTER_SHARP 2
+#define SVT_READ_FILTER_BILINEAR 3
+#define SVT_READ_FILTER_SWITCHABLE 4
+typedef struct svt_frame_read_info {
+    svt_frame_params params;
+    uint32_t uncompressed_bytes, compressed_bytes;
+    uint8_t  show_existing_frame, show_existing_slot;
+    uint8_t  interp_filter;             /* SVT_READ_FILTER_* */
+    uint8_t  tx_mode;
+    uint8_t  needs_backward_adaptation;
+    uint8_t  lossless;
+    uint8_t  pad_[2];
+} svt_frame_read_info;                  /* 80 bytes */
+int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
+                                       svt_frame_read_info *info);
+
+/* The tile of a KEY FRAME read back (host/frame_read.c): the inverse of svt_hip_modes_kf_picture, svt_hip_tokenize_picture and the bool
+ * coder, block by block in coding order -- partition walk, skip flag, intra modes, tokens (the Pareto tail, category bits MSB first,
+ * the sign) -- with every context taken from the grid and eob map filled so far by the writers' own functions.  Outputs, host arrays the
+ * caller sizes, in the formats the stages exchange: lf_mi [mi_rows][mi_stride] as svt_hip_encdec_intra_device takes it (sb_type 0 / 3 / 6 /
+ * 9 / 12, tx_size by the ALLOW_32X32 rule, skip as coded, is_inter 0, modes in pad_[1] / pad_[2] and the nibbles for sb_type 0,
+ * filter_level as given: the header's level after the decoder's delta rule); qcoeff n_sb * SVT_SB_COEFFS position-addressed, zero
+ * wherever nothing was coded; the eob map in the encode pass's layout.  result: leaves, skipped leaves, tokens read (EOB tokens
+ * included), the tile bytes consumed (vpx_reader_find_end) and whether the bool decoder consumed bits beyond the end.
+ * SVT_HIP_ERR_UNSUPPORTED for a rectangular partition.  Never reads at or beyond tile + size, never writes outside the three arrays,
+ * whatever the bytes are: garbage yields an error or a well-formed but meaningless picture. */
+typedef struct svt_tile_read_result {
+    uint32_t leaves, inter_leaves, skipped_leaves, tokens, tile_bytes, past_end;
+    uint32_t odd_candidates; /* inter leaves whose NEARESTMV / NEARMV candidate or NEWMV reference is odd where no high-precision bit applies: a
+                                decoder lowers such a candidate to even (find_best_ref_mvs) and would predict from another MV than the grid's */
+    uint32_t pad_;
+} svt_tile_read_result;                 /* 32 bytes */
+int32_t svt_hip_tile_read_kf_host(const uint8_t *tile, uint32_t size, int32_t width, int32_t height, int32_t mi_stride, int32_t filter_level,
+                                  const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, svt_lf_mode_info *lf_mi, int16_t *qcoeff,
+                                  uint16_t *eob_map, svt_tile_read_result *result);
+
+/* The tile of ANY picture the writers produce, and header plus tile in one call.  An inter picture's tile is the inverse of
+ * svt_hip_modes_inter_picture (csrc/modeinfo_inter_core.h: skip, is_inter, reference frames under the writers' own context functions, the
+ * inter mode under the mode context, MV differences: joint, sign, class, integer bits LSB first, fraction, high-precision bit where
+ * svt_mii_use_mv_hp allows one) with the candidates of every leaf derived by svt_mvr_derive (csrc/mvrefs_core.h) on the grids filled so far.
+ * Outputs beside svt_hip_tile_read_kf_host's: lf_mi with is_inter, luma tx_type 0 in pad_[0] of an inter block (DCT, as the encode pass codes
+ * them), filter_level by the decoder's rule from the header's level and deltas; mc_mi (MVs, ref_list through the inverse of list_ref_frame,
+ * bw8 / bh8; ref_list -1 for an intra unit); ext in svt_hip_mvrefs_batch_device's output format (ref_frame at every unit; mode, ref_mv_*,
+ * mode_context at leaf origins).  NEARESTMV / NEARMV take the candidate as derived, NEWMV adds the difference to slot 0 (a bit that is not coded
+ * reads as set) -- the project's model of section 5.13; result->odd_candidates counts the leaves where a conformant decoder would first lower
+ * the candidate's precision and so end at another MV.
+ * SVT_HIP_ERR_UNSUPPORTED beside the key-frame entry's: lossless, a filter other than the regular one (switchable included), inter blocks
+ * below 8x8, a reference frame with no list in list_ref_frame, a picture size that is no multiple of 8 (frame entry).  Reference scaling
+ * (found_ref, or a size that differs from the reference's) is the header entry's found_ref refusal; reference sizes are not known here.
+ * The same memory-safety contract: nothing at or beyond the input's end is read, nothing outside the arrays written, whatever the bytes. */
+typedef struct svt_tile_read_params {
+    int32_t width, height, mi_stride;
+    uint8_t intra_only;             /* a key frame or an intra-only picture: the key-frame syntax, mc_mi / ext / inter_tables are not touched */
+    uint8_t reference_mode, allow_hp, restrict_ref_mvs;
+    uint8_t interp_filter, lossless; /* as svt_frame_read_info reports them */
+    uint8_t filter_level, mode_ref_delta_enabled;
+    int8_t  ref_deltas[4], mode_deltas[2];
+    uint8_t ref_frame_sign_bias[4];
+    uint8_t list_ref_frame[2];      /* the VP9 reference frame (1 .. 3) REF_LIST_0 / REF_LIST_1 stand for */
+} svt_tile_read_params;             /* 32 bytes */
+int32_t svt_hip_tile_read_host(const uint8_t *tile, uint32_t size, const svt_tile_read_params *params, const svt_bool_tables *bool_tables,
+                               const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables, svt_lf_mode_info *lf_mi,
+                               svt_mc_mode_info *mc_mi, svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result);
+int32_t svt_hip_frame_read_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
+                                int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables,
+                                const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info, svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi,
+                                svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result);
 
 /* one picture of a batch.  header / trailer are HOST bytes (the two headers; up to four show-existing bytes): they travel to the device
  * inside the descriptor upload of the call.  d_tile / d_tile_size are the bool coder's d_bytes / d_size; d_tile may have ANY alignment. */

@@ -247,6 +247,28 @@ class FramePacket(C.Structure):
 
 assert C.sizeof(FrameParams) == 64 and C.sizeof(FramePacket) == 88 and FRAME_ENTRY_DTYPE.itemsize == 8
 
+
+# svt_frame_read_info: what svt_hip_frame_read_header_host returns
+class FrameReadInfo(C.Structure):
+    _fields_ = [("params", FrameParams), ("uncompressed_bytes", C.c_uint32), ("compressed_bytes", C.c_uint32), ("show_existing_frame", C.c_uint8),
+                ("show_existing_slot", C.c_uint8), ("interp_filter", C.c_uint8), ("tx_mode", C.c_uint8), ("needs_backward_adaptation", C.c_uint8),
+                ("lossless", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+assert C.sizeof(FrameReadInfo) == 80
+
+
+class TileReadParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mi_stride", C.c_int32), ("intra_only", C.c_uint8), ("reference_mode", C.c_uint8), ("allow_hp", C.c_uint8),
+                ("restrict_ref_mvs", C.c_uint8), ("interp_filter", C.c_uint8), ("lossless", C.c_uint8), ("filter_level", C.c_uint8), ("mode_ref_delta_enabled", C.c_uint8),
+                ("ref_deltas", C.c_int8 * 4), ("mode_deltas", C.c_int8 * 2), ("ref_frame_sign_bias", C.c_uint8 * 4), ("list_ref_frame", C.c_uint8 * 2)]
+
+
+TILE_READ_RESULT_DTYPE = np.dtype([(n, "<u4") for n in ("leaves", "inter_leaves", "skipped_leaves", "tokens", "tile_bytes", "past_end", "odd_candidates", "pad")])
+assert C.sizeof(TileReadParams) == 32 and TILE_READ_RESULT_DTYPE.itemsize == 32
+READ_FILTER_REGULAR, READ_FILTER_SMOOTH, READ_FILTER_SHARP, READ_FILTER_BILINEAR, READ_FILTER_SWITCHABLE = range(5)
+ERR_BAD_PARAMETER, ERR_UNSUPPORTED = -1, -4
+
 # svt_ois_block (12 bytes): one open-loop intra search record; SVT_OIS_PER_SB per SB (4 x 32x32, 16 x 16x16, 64 x 8x8, 256 x 4x4, z-order)
 OIS_BLOCK_DTYPE = np.dtype([("sad", "<u4"), ("uv_sad", "<u4"), ("mode", "u1"), ("uv_mode", "u1"), ("pad", "u1", (2,))])
 assert OIS_BLOCK_DTYPE.itemsize == 12
@@ -284,6 +306,7 @@ EXPORTS = [
     "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
     "svt_hip_md_inter_modes_batch_device", "svt_hip_md_inter_modes_picture",
     "svt_hip_frame_header_host", "svt_hip_frame_show_existing_host", "svt_hip_frame_batch_device", "svt_hip_frame_assemble_host", "svt_hip_frame_geometry",
+    "svt_hip_recon_batch_device", "svt_hip_decode_batch_device", "svt_hip_frame_read_header_host", "svt_hip_tile_read_kf_host", "svt_hip_tile_read_host", "svt_hip_frame_read_host",
 ]
 
 _lib = None
@@ -334,6 +357,14 @@ def load():
         _lib.svt_hip_host_free.restype = None
         _lib.svt_hip_encdec_work_set_stage_hook.restype = None
         _lib.svt_hip_lf_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.svt_hip_tile_read_kf_host.argtypes = [C.c_void_p, _u32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        _lib.svt_hip_tile_read_host.argtypes = [C.c_void_p, _u32] + [C.c_void_p] * 10
+        _lib.svt_hip_frame_read_host.argtypes = [C.c_void_p, _u32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 11
+        _lib.svt_hip_frame_read_header_host.argtypes = [C.c_void_p, _u32, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (ctx, d_pred, d_recon, d_blocks, size_count[4], d_qtabs, d_qcoeff, d_eob, d_overflow)
+        _lib.svt_hip_recon_batch_device.argtypes = [C.c_void_p] * 9
+        # (ctx, work, n_pics, pics, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status)
+        _lib.svt_hip_decode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     return _lib
 
 

@@ -25,6 +25,8 @@ int32_t svt_set_hip_error(hipError_t e, const char *file, int line) {
     return SVT_HIP_ERR_DEVICE;
 }
 extern "C" const char *svt_hip_last_error(void) { return g_err; }
+/* the same for the plain-C host stages (host/frame_read.c); internal, not part of the header */
+extern "C" int32_t svt_set_error_c(int32_t code, const char *msg) { return svt_set_error(code, msg); }
 
 extern "C" int32_t svt_hip_sb_count(int32_t w, int32_t h) { return ((w + 63) / 64) * ((h + 63) / 64); }
 

@@ -292,48 +292,82 @@ extern "C" void svt_hip_encdec_work_destroy(svt_hip_ctx *ctx, svt_encdec_work *w
     free(w);
 }
 
-extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
-                                               int32_t height, int32_t mi_stride, int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr,
-                                               int32_t pad_x, int32_t pad_y) {
+/* profiling hook at a stage boundary of the batch entries (svt_hip_encdec_work_set_stage_hook); w: the workspace */
+#define ED_STAGE(k) do { if (w->hook) w->hook(w->hook_user, (k)); } while (0)
+
+namespace {
+
+/* what a batch entry hands to its launches: the parameter block (host copy and its device twin), the base pointers of the batch's
+ * 32-bit offset spaces and the per-picture descriptors of the stages behind the transform */
+struct ed_setup {
+    ed_batch_dev        hb;
+    const ed_batch_dev *dB;
+    uintptr_t           src_lo, pred_lo, q_lo, dq_lo;
+    uint8_t            *recon_set[ED_MAX_SETS];
+    int                 n_sets;
+    svt_mc_picture      mcp[ED_MAX_PICS];
+    svt_yuv_planes      rec[ED_MAX_PICS], rec_pad[ED_MAX_PICS];
+    int                 n_rec_pad;
+    const svt_lf_mask  *lfm[ED_MAX_PICS];
+    int32_t             lfm_stride[ED_MAX_PICS], mi_rows_a[ED_MAX_PICS], mi_cols_a[ED_MAX_PICS];
+};
+
+/* Argument checking and descriptor set-up of svt_hip_encdec_batch_device and svt_hip_decode_batch_device: everything in front of the
+ * first launch, the parameter block and the q index's tables sent.  decode: the pictures' src and d_dqcoeff are not looked at (the source
+ * offsets of the geometry records read 0) and a picture with has_intra is refused. */
+/* an error of ed_prepare under the name of the entry that called it: "encdec: ..." as before, "decode: ..." for the decode pass */
+int32_t ed_bad(bool decode, const char *what, int32_t code = SVT_HIP_ERR_BAD_PARAMETER) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", decode ? "decode" : "encdec", what);
+    return svt_set_error(code, msg);
+}
+
+int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width, int32_t height, int32_t mi_stride,
+                   int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr, const bool decode, ed_setup &S) {
     if (!ctx || !w || !pics || !flags || n_pics < 1 || n_pics > w->max_pics || width != w->width || height != w->height || mi_stride < (width >> 3))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: bad argument");
-    if (flags->apply_loop_filter && !thr) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: loop filter without thresholds");
+        return ed_bad(decode, "bad argument");
+    if (flags->apply_loop_filter && !thr) return ed_bad(decode, "loop filter without thresholds");
+    if (decode)
+        for (int i = 0; i < n_pics; i++)
+            if (pics[i].has_intra) return svt_set_error(SVT_HIP_ERR_UNSUPPORTED, "decode: pictures with intra blocks are not reconstructed by this entry");
     HIP_TRY(hipSetDevice(ctx->device));
     /* one 32-bit offset space for the source planes and one for the prediction planes of the batch */
     uintptr_t src_lo = UINTPTR_MAX, src_hi = 0, pred_lo = UINTPTR_MAX, pred_hi = 0;
     for (int i = 0; i < n_pics; i++) {
         const svt_encdec_picture &p = pics[i];
-        if (!p.d_mc_mi || !p.d_lf_mi || !p.src.y || !p.src.u || !p.src.v || !p.pred.y || !p.pred.u || !p.pred.v || !p.recon.y || !p.recon.u || !p.recon.v ||
+        if (!p.d_mc_mi || !p.d_lf_mi || (!decode && (!p.src.y || !p.src.u || !p.src.v)) || !p.pred.y || !p.pred.u || !p.pred.v || !p.recon.y || !p.recon.u || !p.recon.v ||
             !p.d_qcoeff || !p.d_eob_map || !p.d_nz || (flags->apply_loop_filter && !p.d_lfm))
-            return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: null picture field");
-        if (!p.d_dqcoeff != !pics[0].d_dqcoeff) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: d_dqcoeff must be given for every picture of a batch or for none");
-        if (((uintptr_t)p.d_qcoeff | (uintptr_t)p.d_dqcoeff) & 15) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: coefficient arrays must be 16-byte aligned");
+            return ed_bad(decode, "null picture field");
+        if (!decode && !p.d_dqcoeff != !pics[0].d_dqcoeff) return ed_bad(decode, "d_dqcoeff must be given for every picture of a batch or for none");
+        if (((uintptr_t)p.d_qcoeff | (decode ? 0 : (uintptr_t)p.d_dqcoeff)) & 15) return ed_bad(decode, "coefficient arrays must be 16-byte aligned");
         const uint8_t *s3[3] = {p.src.y, p.src.u, p.src.v}, *p3[3] = {p.pred.y, p.pred.u, p.pred.v};
         for (int k = 0; k < 3; k++) {
-            src_lo = (uintptr_t)s3[k] < src_lo ? (uintptr_t)s3[k] : src_lo; src_hi = (uintptr_t)s3[k] > src_hi ? (uintptr_t)s3[k] : src_hi;
+            if (!decode) { src_lo = (uintptr_t)s3[k] < src_lo ? (uintptr_t)s3[k] : src_lo; src_hi = (uintptr_t)s3[k] > src_hi ? (uintptr_t)s3[k] : src_hi; }
             pred_lo = (uintptr_t)p3[k] < pred_lo ? (uintptr_t)p3[k] : pred_lo; pred_hi = (uintptr_t)p3[k] > pred_hi ? (uintptr_t)p3[k] : pred_hi;
         }
     }
+    if (decode) src_lo = src_hi = 0;
     /* bytes from a plane's first sample to its last row's end: the largest stride x rows among the planes the 32-bit block offsets
        address (a reference buffer's stride is width + 160; a caller's stride can exceed 2 x width on narrow pictures) */
     uint64_t plane_span = 0;
     for (int i = 0; i < n_pics; i++) {
         const svt_yuv_planes *pl[3] = {&pics[i].src, &pics[i].pred, &pics[i].recon};
-        for (int k = 0; k < 3; k++) {
+        for (int k = decode ? 1 : 0; k < 3; k++) {
             const uint64_t a = (uint64_t)(pl[k]->y_stride > 0 ? pl[k]->y_stride : 0) * (uint64_t)height, b = (uint64_t)(pl[k]->uv_stride > 0 ? pl[k]->uv_stride : 0) * (uint64_t)(height / 2);
             plane_span = a > plane_span ? a : plane_span;
             plane_span = b > plane_span ? b : plane_span;
         }
     }
     if ((uint64_t)(src_hi - src_lo) + plane_span >= (1ull << 32) || (uint64_t)(pred_hi - pred_lo) + plane_span >= (1ull << 32))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: the batch's source / prediction planes must lie within 4 GB");
+        return ed_bad(decode, "the batch's source / prediction planes must lie within 4 GB");
     /* coefficient arrays: one base for the batch as well (element offsets are 32 bit) */
     uintptr_t q_lo = UINTPTR_MAX, dq_lo = UINTPTR_MAX;
     for (int i = 0; i < n_pics; i++) {
         q_lo = (uintptr_t)pics[i].d_qcoeff < q_lo ? (uintptr_t)pics[i].d_qcoeff : q_lo;
-        dq_lo = (uintptr_t)pics[i].d_dqcoeff < dq_lo ? (uintptr_t)pics[i].d_dqcoeff : dq_lo;
+        if (!decode) dq_lo = (uintptr_t)pics[i].d_dqcoeff < dq_lo ? (uintptr_t)pics[i].d_dqcoeff : dq_lo;
     }
-    ed_batch_dev hb;
+    if (decode) dq_lo = 0;
+    ed_batch_dev &hb = S.hb;
     memset(&hb, 0, sizeof hb);
     fill_dims(hb, n_pics, width, height, mi_stride);
     {
@@ -344,7 +378,7 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     /* reconstruction bases: at most ED_MAX_SETS pointers, each serving every picture whose planes lie within 4 GB above it.  Chosen
        from the pictures' lowest plane addresses in ascending order, so that the result does not depend on the order the pictures
        arrive in (separately allocated buffers in descending address order once opened a base each) */
-    uint8_t       *recon_set[ED_MAX_SETS];
+    uint8_t      **recon_set = S.recon_set;
     int            n_sets = 0;
     {
         uintptr_t lo[ED_MAX_PICS], hi[ED_MAX_PICS];
@@ -360,22 +394,22 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
             const int i = order[a];
             if (n_sets && (uint64_t)(hi[i] - (uintptr_t)recon_set[n_sets - 1]) + plane_span < (1ull << 32)) continue; /* (sorted: lo[i] >= the last base) */
             if (n_sets == ED_MAX_SETS || (uint64_t)(hi[i] - lo[i]) + plane_span >= (1ull << 32))
-                return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: the batch's reconstruction buffers span more than 8 regions of 4 GB");
+                return ed_bad(decode, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
             recon_set[n_sets++] = (uint8_t *)lo[i];
         }
     }
-    svt_mc_picture mcp[ED_MAX_PICS];
-    svt_yuv_planes rec[ED_MAX_PICS], rec_pad[ED_MAX_PICS];
+    svt_mc_picture *mcp = S.mcp;
+    svt_yuv_planes *rec = S.rec, *rec_pad = S.rec_pad;
     int            n_rec_pad = 0;
-    const svt_lf_mask *lfm[ED_MAX_PICS];
-    int32_t        lfm_stride[ED_MAX_PICS], mi_rows_a[ED_MAX_PICS], mi_cols_a[ED_MAX_PICS];
+    const svt_lf_mask **lfm = S.lfm;
+    int32_t       *lfm_stride = S.lfm_stride, *mi_rows_a = S.mi_rows_a, *mi_cols_a = S.mi_cols_a;
     for (int i = 0; i < n_pics; i++) {
         const svt_encdec_picture &p = pics[i];
         ed_pic_dev &P = hb.pic[i];
         P.mc_mi = (svt_mc_mode_info *)p.d_mc_mi; P.lf_mi = p.d_lf_mi; P.nz = p.d_nz; P.eob_map = p.d_eob_map; P.lfm = p.d_lfm;
-        const uintptr_t q_off = ((uintptr_t)p.d_qcoeff - q_lo) / sizeof(int16_t), dq_off = ((uintptr_t)p.d_dqcoeff - dq_lo) / sizeof(int16_t);
-        if ((p.d_dqcoeff && q_off != dq_off) || q_off + (uint64_t)hb.n_sb * SVT_SB_COEFFS >= (1ull << 32))
-            return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: qcoeff / dqcoeff of the batch must be laid out alike, within 2^32 elements");
+        const uintptr_t q_off = ((uintptr_t)p.d_qcoeff - q_lo) / sizeof(int16_t), dq_off = decode ? q_off : ((uintptr_t)p.d_dqcoeff - dq_lo) / sizeof(int16_t);
+        if ((!decode && p.d_dqcoeff && q_off != dq_off) || q_off + (uint64_t)hb.n_sb * SVT_SB_COEFFS >= (1ull << 32))
+            return ed_bad(decode, "qcoeff / dqcoeff of the batch must be laid out alike, within 2^32 elements");
         /* the picture's reconstruction planes: 32-bit offsets from one of at most ED_MAX_SETS base pointers (a base serves every
            picture whose planes lie within 4 GB above it: buffers carved out of one slab share one) */
         const uint8_t *r3[3] = {p.recon.y, p.recon.u, p.recon.v};
@@ -384,15 +418,15 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
         int set = -1;
         for (int k = n_sets - 1; k >= 0 && set < 0; k--) /* the highest base at or below the picture: the one chosen for it above */
             if (r_lo >= (uintptr_t)recon_set[k] && (uint64_t)(r_hi - (uintptr_t)recon_set[k]) + plane_span < (1ull << 32)) set = k;
-        if (set < 0) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: the batch's reconstruction buffers span more than 8 regions of 4 GB");
+        if (set < 0) return ed_bad(decode, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
         svt_tq_pic_geom &g = P.g;
         const uint8_t *s3[3] = {p.src.y, p.src.u, p.src.v}, *p3[3] = {p.pred.y, p.pred.u, p.pred.v};
         for (int k = 0; k < 3; k++) {
-            g.src_off[k] = (uint32_t)((uintptr_t)s3[k] - src_lo); g.pred_off[k] = (uint32_t)((uintptr_t)p3[k] - pred_lo);
+            g.src_off[k] = decode ? 0u : (uint32_t)((uintptr_t)s3[k] - src_lo); g.pred_off[k] = (uint32_t)((uintptr_t)p3[k] - pred_lo);
             g.recon_off[k] = (uint32_t)((uintptr_t)r3[k] - (uintptr_t)recon_set[set]);
         }
-        if (p.src.y_stride > 65535 || p.pred.y_stride > 65535 || p.recon.y_stride > 65535) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: stride");
-        g.src_stride[0] = (uint16_t)p.src.y_stride; g.src_stride[1] = (uint16_t)p.src.uv_stride;
+        if ((!decode && p.src.y_stride > 65535) || p.pred.y_stride > 65535 || p.recon.y_stride > 65535) return ed_bad(decode, "stride");
+        g.src_stride[0] = decode ? 0 : (uint16_t)p.src.y_stride; g.src_stride[1] = decode ? 0 : (uint16_t)p.src.uv_stride;
         g.pred_stride[0] = (uint16_t)p.pred.y_stride; g.pred_stride[1] = (uint16_t)p.pred.uv_stride;
         g.recon_stride[0] = (uint16_t)p.recon.y_stride; g.recon_stride[1] = (uint16_t)p.recon.uv_stride;
         g.coeff_base = (uint32_t)q_off; g.width = width; g.height = height; g.recon_set = (uint8_t)set; g.pic = (uint8_t)i; g.do_recon = flags->do_recon ? 1 : 0;
@@ -403,17 +437,36 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
         lfm[i] = p.d_lfm; lfm_stride[i] = hb.sb_cols; mi_rows_a[i] = hb.mi_rows; mi_cols_a[i] = hb.mi_cols;
     }
     const ed_batch_dev *dB = nullptr;
-    if (stage_batch(ctx, hb, &dB)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec: descriptor buffers");
+    if (stage_batch(ctx, hb, &dB)) return ed_bad(decode, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
     /* quantiser tables of the q index */
     {
         svt_quant_tables qt[2];
-        if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec: q index");
+        if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return ed_bad(decode, "q index");
         void *h = nullptr, *d = nullptr;
-        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec: descriptor buffers");
+        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return ed_bad(decode, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
         memcpy(h, qt, sizeof qt);
         HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
     }
-#define ED_STAGE(k) do { if (w->hook) w->hook(w->hook_user, (k)); } while (0)
+    S.dB = dB; S.src_lo = src_lo; S.pred_lo = pred_lo; S.q_lo = q_lo; S.dq_lo = dq_lo; S.n_sets = n_sets; S.n_rec_pad = n_rec_pad;
+    return SVT_HIP_OK;
+}
+
+} // namespace
+
+extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                               int32_t height, int32_t mi_stride, int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr,
+                                               int32_t pad_x, int32_t pad_y) {
+    ed_setup S;
+    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, flags, thr, false, S)) return e;
+    const ed_batch_dev &hb = S.hb;
+    const ed_batch_dev *dB = S.dB;
+    const uintptr_t     src_lo = S.src_lo, pred_lo = S.pred_lo, q_lo = S.q_lo, dq_lo = S.dq_lo;
+    uint8_t *const     *recon_set = S.recon_set;
+    const int           n_sets = S.n_sets, n_rec_pad = S.n_rec_pad;
+    const svt_mc_picture *mcp = S.mcp;
+    const svt_yuv_planes *rec = S.rec, *rec_pad = S.rec_pad;
+    const svt_lf_mask *const *lfm = S.lfm;
+    const int32_t      *lfm_stride = S.lfm_stride, *mi_rows_a = S.mi_rows_a, *mi_cols_a = S.mi_cols_a;
     /* 1. inter prediction of the whole batch */
     ED_STAGE(SVT_ENCDEC_STAGE_MC);
     int32_t rc = svt_hip_inter_pred_batch_device(ctx, n_pics, mcp);
@@ -474,6 +527,85 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     ED_STAGE(SVT_ENCDEC_STAGE_PAD);
     if (flags->pad_reference && n_rec_pad) {
         rc = svt_hip_ref_pad_batch_device(ctx, n_rec_pad, rec_pad, pad_x, pad_y);
+        if (rc) return rc;
+    }
+    ED_STAGE(SVT_ENCDEC_STAGE_END);
+    return SVT_HIP_OK;
+}
+
+namespace {
+/* the decode pass takes inter leaves only: a unit inside the picture whose record says is_inter = 0 is reported (its blocks are in no list) */
+__global__ __launch_bounds__(256) void svt_dec_intra_check_kernel(const ed_batch_dev *__restrict__ B, int32_t *__restrict__ status) {
+    const int units = B->mi_rows * B->mi_cols;
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= units * B->n_pics) return;
+    const int pic = i / units, u = i % units;
+    if (!B->pic[pic].lf_mi[(u / B->mi_cols) * B->mi_stride + u % B->mi_cols].is_inter) atomicOr(status, 1);
+}
+} // namespace
+
+/* The decode pass: a batch of inter pictures rebuilt from what a frame reader returned (include/svtvp9_hip.h).  The stages and their
+ * order are the encode pass's, with svt_rc_kernel (recon_kernel.hip) in the place of the forward transform: the eob maps are inputs here
+ * (not cleared), the reconstruction kernel leaves every block's eob in list order, and svt_tq_skip_kernel + svt_skip_update_kernel then
+ * state exactly the decoder's rule -- an inter leaf of 8x8 or larger with no coefficient in any of its transform blocks is skipped for
+ * the loop filter (vp9_decodeframe.c: decode_block resets mi->skip of such a leaf only when eobtotal is 0 and the leaf is >= 8x8; the
+ * lists hold nothing below 8x8 that is inter).  svt_tq_skip_kernel's rewrite of the eob map entries stores the values it was read from. */
+extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                               int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
+                                               int32_t *d_status) {
+    if (!d_status) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode: null status");
+    svt_encdec_flags flags;
+    memset(&flags, 0, sizeof flags);
+    flags.do_recon = 1; flags.apply_loop_filter = thr ? 1 : 0; flags.pad_reference = 1;
+    ed_setup S;
+    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, &flags, thr, true, S)) return e;
+    const ed_batch_dev &hb = S.hb;
+    const ed_batch_dev *dB = S.dB;
+    HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
+    /* 1. inter prediction of the whole batch */
+    ED_STAGE(SVT_ENCDEC_STAGE_MC);
+    int32_t rc = svt_hip_inter_pred_batch_device(ctx, n_pics, S.mcp);
+    if (rc) return rc;
+    /* 2. transform blocks from the grids */
+    ED_STAGE(SVT_ENCDEC_STAGE_LISTS);
+    const int nwg = n_pics * hb.n_sb;
+    hipLaunchKernelGGL(svt_tq_count_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_counts, w->d_status);
+    hipLaunchKernelGGL(svt_scan_sb_kernel, dim3(4 * n_pics), dim3(256), 0, ctx->stream, w->d_counts, hb.n_sb, w->d_totals);
+    hipLaunchKernelGGL(svt_scan_pic_kernel, dim3(1), dim3(64), 0, ctx->stream, (const int32_t *)w->d_totals, n_pics, w->d_bases, w->d_off_cnt);
+    hipLaunchKernelGGL(svt_tq_emit_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, (const int32_t *)w->d_counts, (const int32_t *)w->d_bases, (svt_tq_block *)nullptr, w->d_pos);
+    hipLaunchKernelGGL(svt_dec_intra_check_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB, w->d_status);
+    HIP_TRY(hipGetLastError());
+    if (!w->last_hb) w->last_hb = malloc(sizeof hb);
+    if (w->last_hb) memcpy(w->last_hb, &hb, sizeof hb);
+    /* 3. coefficients -> dequantisation -> inverse transform -> reconstruction; d_status[0] = coefficients that overflowed 16 bits */
+    ED_STAGE(SVT_ENCDEC_STAGE_TQ);
+    int32_t cap[4];
+    for (int s = 0; s < 4; s++) cap[s] = (int32_t)((size_t)n_pics * width * height * 3 / 2 / (size_t)(16 << (2 * s)));
+    rc = svt_rc_launch_device_lists(ctx, (const uint8_t *)S.pred_lo, S.recon_set, S.n_sets, cap, w->d_off_cnt, w->d_qtabs, (const int16_t *)S.q_lo, w->d_eob, w->d_pos,
+                                    &dB->pic[0].g, &dB->pic[0].eob_map, (int)sizeof(ed_pic_dev), dB->iscan_off, hb.sb_cols, (uint32_t *)d_status);
+    if (rc) return rc;
+    /* 4. skip flags from the eobs (above) */
+    ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
+    {
+        const int total_cap = (int)(w->cap_per_pic * (size_t)n_pics);
+        int       g = (total_cap + 255) / 256;
+        if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
+        hipLaunchKernelGGL(svt_tq_skip_kernel, dim3(g), dim3(256), 0, ctx->stream, dB, (const int32_t *)w->d_off_cnt, (const uint32_t *)w->d_pos, (const uint16_t *)w->d_eob);
+        hipLaunchKernelGGL(svt_skip_update_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
+        HIP_TRY(hipGetLastError());
+    }
+    /* 5. deblocking (thr = NULL: the header's filter level is 0) */
+    ED_STAGE(SVT_ENCDEC_STAGE_LF);
+    if (thr) {
+        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_status);
+        HIP_TRY(hipGetLastError());
+        rc = svt_hip_lf_batch_device(ctx, n_pics, S.rec, S.lfm, S.lfm_stride, thr, S.mi_rows_a, S.mi_cols_a, 0);
+        if (rc) return rc;
+    }
+    /* 6. the reconstruction becomes a reference picture */
+    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
+    if (S.n_rec_pad) {
+        rc = svt_hip_ref_pad_batch_device(ctx, S.n_rec_pad, S.rec_pad, pad_x, pad_y);
         if (rc) return rc;
     }
     ED_STAGE(SVT_ENCDEC_STAGE_END);

@@ -105,6 +105,11 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
                                    const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, uint64_t *d_dist,
                                    const uint32_t *d_pos, const void *d_geom, int geom_stride, const uint32_t *d_iscan_off, int sb_cols);
 
+/* reconstruction from coefficients over device-built block lists (recon_kernel.hip; used by encdec.hip's decode pass) */
+int32_t svt_rc_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set, const int32_t cap[4], const int32_t *d_off_cnt,
+                                   const svt_quant_tables *d_qtabs, const int16_t *d_qcoeff, uint16_t *d_eob_list, const uint32_t *d_pos, const void *d_geom,
+                                   const void *d_eob_maps, int geom_stride, const uint32_t *d_iscan_off, int sb_cols, uint32_t *d_overflow);
+
 /* encode pass of an intra picture / the stand-in intra decision (intra_kernel.hip; used by encdec.hip).  d_sync: 2 + 3 * (number of
  * 16x16 luma cells) dwords of scratch */
 int32_t svt_intra_launch(svt_hip_ctx *ctx, const svt_encdec_picture *p, int32_t width, int32_t height, int32_t mi_stride, const svt_quant_tables *d_qtabs,
