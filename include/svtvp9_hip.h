@@ -1264,12 +1264,34 @@ int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work *work, int
  * For the grids, coefficients and eob maps an encode pass left (do_recon, and apply_loop_filter / pad_reference as here) the planes, the
  * masks and the skip flags equal that pass's byte for byte.
  * d_status (device, required): d_status[0] = the number of coefficients whose dequantised value overflowed 16 bits (0 for a
- * conformant stream).  A picture with has_intra is refused (SVT_HIP_ERR_UNSUPPORTED) before anything is launched; a grid that holds an
- * is_inter = 0 leaf all the same, or is malformed, is reported by svt_hip_encdec_work_status, its blocks left out.  Intra blocks need a
- * coefficient-driven form of the wavefront kernel. */
+ * conformant stream).  A picture with has_intra is refused (SVT_HIP_ERR_UNSUPPORTED) before anything is launched -- this entry is the
+ * pass for batches known to hold inter leaves only; svt_hip_decode_mixed_batch_device below takes the others.  A grid that holds an
+ * is_inter = 0 leaf all the same, or is malformed, is reported by svt_hip_encdec_work_status, its blocks left out. */
 int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work *work, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
                                     int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
                                     int32_t *d_status);
+/* The same pass for batches whose pictures may carry has_intra (inter pictures with intra leaves): same arguments, stages and outputs.
+ * Behind the reconstruction of the inter leaves and in front of the skip flags, the intra leaves of every picture with has_intra are
+ * predicted and reconstructed from their coefficients by the wavefront kernel of svt_hip_decode_intra_device, one picture after the other
+ * -- the place and order of svt_hip_encdec_batch_device's intra step.  Planes and strides of a picture with has_intra must be 4-byte
+ * aligned.  An is_inter = 0 leaf in a picture whose has_intra is 0 is still reported by svt_hip_encdec_work_status; d_status[0] counts
+ * the overflowed coefficients of inter and intra blocks together. */
+int32_t svt_hip_decode_mixed_batch_device(svt_hip_ctx *ctx, svt_encdec_work *work, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                          int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
+                                          int32_t *d_status);
+/* The decode pass of an INTRA picture (key frames, intra-refresh pictures): the decode twin of svt_hip_encdec_intra_device below, on the
+ * same grid format.  INPUTS: pic->d_lf_mi, d_qcoeff (zero wherever nothing was coded), d_eob_map; src, d_dqcoeff, d_mc_mi and ref are not
+ * looked at.  WRITTEN: pred (may be all NULL: the prediction is then not stored), recon, the grid's `skip`, d_nz, d_lfm.  Stages,
+ * asynchronous on the context's stream: d_status[0] cleared -> reference samples + predictor + dequantisation / inverse transform /
+ * reconstruction of every block in the encode pass's dependency order (each block's eob read from the eob map; eob 0: the prediction is the
+ * reconstruction) -> skip flags (a block with no coefficient in any of its transform blocks is skipped) -> thr != NULL: masks +
+ * deblocking -> border of pad_x / pad_y samples unless pic->no_pad.  For the grid, coefficients and eob map an encode pass left, the planes,
+ * masks and skip flags equal that pass's byte for byte.  The above-right rule is the encode pass's (none for blocks >= 8x8).
+ * d_status (device, required): d_status[0] = coefficients whose dequantised value overflowed 16 bits.  A malformed grid (a 64x64 or
+ * rectangular block, an inter leaf ...) is reported by svt_hip_encdec_work_status; the pass terminates whatever the grid and the
+ * coefficient arrays hold.  d_qcoeff 16-byte aligned; planes and strides 4-byte aligned. */
+int32_t svt_hip_decode_intra_device(svt_hip_ctx *ctx, svt_encdec_work *work, const svt_encdec_picture *pic, int32_t width, int32_t height,
+                                    int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y, int32_t *d_status);
 /* The encode pass of an INTRA picture (key frames, intra-refresh pictures): reference samples + the ten VP9 intra predictors +
  * transform / quantisation / reconstruction of every block in coding-dependency order (encode_pass_sb with intra blocks,
  * Codec/EbEncDecProcess.c:3680-4160: generate_intra_reference_samples :1128, intra_prediction Codec/EbIntraPrediction.c:16 ->

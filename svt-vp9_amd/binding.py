@@ -306,7 +306,7 @@ EXPORTS = [
     "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
     "svt_hip_md_inter_modes_batch_device", "svt_hip_md_inter_modes_picture",
     "svt_hip_frame_header_host", "svt_hip_frame_show_existing_host", "svt_hip_frame_batch_device", "svt_hip_frame_assemble_host", "svt_hip_frame_geometry",
-    "svt_hip_recon_batch_device", "svt_hip_decode_batch_device", "svt_hip_frame_read_header_host", "svt_hip_tile_read_kf_host", "svt_hip_tile_read_host", "svt_hip_frame_read_host",
+    "svt_hip_recon_batch_device", "svt_hip_decode_batch_device", "svt_hip_decode_mixed_batch_device", "svt_hip_decode_intra_device", "svt_hip_frame_read_header_host", "svt_hip_tile_read_kf_host", "svt_hip_tile_read_host", "svt_hip_frame_read_host",
 ]
 
 _lib = None
@@ -365,6 +365,9 @@ def load():
         _lib.svt_hip_recon_batch_device.argtypes = [C.c_void_p] * 9
         # (ctx, work, n_pics, pics, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status)
         _lib.svt_hip_decode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        _lib.svt_hip_decode_mixed_batch_device.argtypes = _lib.svt_hip_decode_batch_device.argtypes
+        # (ctx, work, pic, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status)
+        _lib.svt_hip_decode_intra_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     return _lib
 
 

@@ -314,7 +314,8 @@ struct ed_setup {
 
 /* Argument checking and descriptor set-up of svt_hip_encdec_batch_device and svt_hip_decode_batch_device: everything in front of the
  * first launch, the parameter block and the q index's tables sent.  decode: the pictures' src and d_dqcoeff are not looked at (the source
- * offsets of the geometry records read 0) and a picture with has_intra is refused. */
+ * offsets of the geometry records read 0) and a picture with has_intra is refused unless allow_intra (svt_hip_decode_mixed_batch_device:
+ * such a picture's planes and strides must then be 4-byte aligned, what the wavefront kernel's dword accesses need). */
 /* an error of ed_prepare under the name of the entry that called it: "encdec: ..." as before, "decode: ..." for the decode pass */
 int32_t ed_bad(bool decode, const char *what, int32_t code = SVT_HIP_ERR_BAD_PARAMETER) {
     char msg[160];
@@ -323,11 +324,11 @@ int32_t ed_bad(bool decode, const char *what, int32_t code = SVT_HIP_ERR_BAD_PAR
 }
 
 int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width, int32_t height, int32_t mi_stride,
-                   int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr, const bool decode, ed_setup &S) {
+                   int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr, const bool decode, const bool allow_intra, ed_setup &S) {
     if (!ctx || !w || !pics || !flags || n_pics < 1 || n_pics > w->max_pics || width != w->width || height != w->height || mi_stride < (width >> 3))
         return ed_bad(decode, "bad argument");
     if (flags->apply_loop_filter && !thr) return ed_bad(decode, "loop filter without thresholds");
-    if (decode)
+    if (decode && !allow_intra)
         for (int i = 0; i < n_pics; i++)
             if (pics[i].has_intra) return svt_set_error(SVT_HIP_ERR_UNSUPPORTED, "decode: pictures with intra blocks are not reconstructed by this entry");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -340,6 +341,10 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
             return ed_bad(decode, "null picture field");
         if (!decode && !p.d_dqcoeff != !pics[0].d_dqcoeff) return ed_bad(decode, "d_dqcoeff must be given for every picture of a batch or for none");
         if (((uintptr_t)p.d_qcoeff | (decode ? 0 : (uintptr_t)p.d_dqcoeff)) & 15) return ed_bad(decode, "coefficient arrays must be 16-byte aligned");
+        if (decode && p.has_intra &&
+            (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v |
+              (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride | (uintptr_t)p.recon.y_stride | (uintptr_t)p.recon.uv_stride) & 3))
+            return ed_bad(decode, "planes and strides of a picture with intra blocks must be 4-byte aligned");
         const uint8_t *s3[3] = {p.src.y, p.src.u, p.src.v}, *p3[3] = {p.pred.y, p.pred.u, p.pred.v};
         for (int k = 0; k < 3; k++) {
             if (!decode) { src_lo = (uintptr_t)s3[k] < src_lo ? (uintptr_t)s3[k] : src_lo; src_hi = (uintptr_t)s3[k] > src_hi ? (uintptr_t)s3[k] : src_hi; }
@@ -457,7 +462,7 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
                                                int32_t height, int32_t mi_stride, int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr,
                                                int32_t pad_x, int32_t pad_y) {
     ed_setup S;
-    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, flags, thr, false, S)) return e;
+    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, flags, thr, false, false, S)) return e;
     const ed_batch_dev &hb = S.hb;
     const ed_batch_dev *dB = S.dB;
     const uintptr_t     src_lo = S.src_lo, pred_lo = S.pred_lo, q_lo = S.q_lo, dq_lo = S.dq_lo;
@@ -534,33 +539,34 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
 }
 
 namespace {
-/* the decode pass takes inter leaves only: a unit inside the picture whose record says is_inter = 0 is reported (its blocks are in no list) */
-__global__ __launch_bounds__(256) void svt_dec_intra_check_kernel(const ed_batch_dev *__restrict__ B, int32_t *__restrict__ status) {
+/* the lists of the decode pass hold inter leaves only: a unit inside the picture whose record says is_inter = 0 is reported (its blocks are
+ * in no list) unless its picture's bit of intra_mask is set (has_intra: the wavefront kernel reconstructs them) */
+__global__ __launch_bounds__(256) void svt_dec_intra_check_kernel(const ed_batch_dev *__restrict__ B, int32_t *__restrict__ status, const uint32_t intra_mask) {
     const int units = B->mi_rows * B->mi_cols;
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= units * B->n_pics) return;
     const int pic = i / units, u = i % units;
+    if ((intra_mask >> pic) & 1) return;
     if (!B->pic[pic].lf_mi[(u / B->mi_cols) * B->mi_stride + u % B->mi_cols].is_inter) atomicOr(status, 1);
 }
-} // namespace
-
 /* The decode pass: a batch of inter pictures rebuilt from what a frame reader returned (include/svtvp9_hip.h).  The stages and their
  * order are the encode pass's, with svt_rc_kernel (recon_kernel.hip) in the place of the forward transform: the eob maps are inputs here
  * (not cleared), the reconstruction kernel leaves every block's eob in list order, and svt_tq_skip_kernel + svt_skip_update_kernel then
  * state exactly the decoder's rule -- an inter leaf of 8x8 or larger with no coefficient in any of its transform blocks is skipped for
  * the loop filter (vp9_decodeframe.c: decode_block resets mi->skip of such a leaf only when eobtotal is 0 and the leaf is >= 8x8; the
  * lists hold nothing below 8x8 that is inter).  svt_tq_skip_kernel's rewrite of the eob map entries stores the values it was read from. */
-extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
-                                               int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
-                                               int32_t *d_status) {
+int32_t decode_batch(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width, int32_t height, int32_t mi_stride,
+                     int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y, int32_t *d_status, const bool allow_intra) {
     if (!d_status) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode: null status");
     svt_encdec_flags flags;
     memset(&flags, 0, sizeof flags);
     flags.do_recon = 1; flags.apply_loop_filter = thr ? 1 : 0; flags.pad_reference = 1;
     ed_setup S;
-    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, &flags, thr, true, S)) return e;
+    if (const int32_t e = ed_prepare(ctx, w, n_pics, pics, width, height, mi_stride, q_index, &flags, thr, true, allow_intra, S)) return e;
     const ed_batch_dev &hb = S.hb;
     const ed_batch_dev *dB = S.dB;
+    uint32_t intra_mask = 0; /* (ED_MAX_PICS = 32 pictures: one bit each) */
+    for (int i = 0; i < n_pics; i++) intra_mask |= pics[i].has_intra ? 1u << i : 0u;
     HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
     /* 1. inter prediction of the whole batch */
     ED_STAGE(SVT_ENCDEC_STAGE_MC);
@@ -573,7 +579,7 @@ extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     hipLaunchKernelGGL(svt_scan_sb_kernel, dim3(4 * n_pics), dim3(256), 0, ctx->stream, w->d_counts, hb.n_sb, w->d_totals);
     hipLaunchKernelGGL(svt_scan_pic_kernel, dim3(1), dim3(64), 0, ctx->stream, (const int32_t *)w->d_totals, n_pics, w->d_bases, w->d_off_cnt);
     hipLaunchKernelGGL(svt_tq_emit_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, (const int32_t *)w->d_counts, (const int32_t *)w->d_bases, (svt_tq_block *)nullptr, w->d_pos);
-    hipLaunchKernelGGL(svt_dec_intra_check_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB, w->d_status);
+    hipLaunchKernelGGL(svt_dec_intra_check_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB, w->d_status, intra_mask);
     HIP_TRY(hipGetLastError());
     if (!w->last_hb) w->last_hb = malloc(sizeof hb);
     if (w->last_hb) memcpy(w->last_hb, &hb, sizeof hb);
@@ -584,6 +590,13 @@ extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     rc = svt_rc_launch_device_lists(ctx, (const uint8_t *)S.pred_lo, S.recon_set, S.n_sets, cap, w->d_off_cnt, w->d_qtabs, (const int16_t *)S.q_lo, w->d_eob, w->d_pos,
                                     &dB->pic[0].g, &dB->pic[0].eob_map, (int)sizeof(ed_pic_dev), dB->iscan_off, hb.sb_cols, (uint32_t *)d_status);
     if (rc) return rc;
+    /* 3b. intra blocks of inter pictures: their inter neighbours are reconstructed now; the coefficient-driven wavefront kernel rebuilds them,
+           one picture after the other (it marks their units' coefficient flags itself; the eob map is its input) */
+    for (int i = 0; i < n_pics; i++)
+        if (pics[i].has_intra) {
+            rc = svt_intra_rc_launch(ctx, &pics[i], width, height, mi_stride, w->d_qtabs, hb.iscan_off, w->d_intra_sync, w->d_status, (uint32_t *)d_status, 1);
+            if (rc) return rc;
+        }
     /* 4. skip flags from the eobs (above) */
     ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
     {
@@ -606,6 +619,83 @@ extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     ED_STAGE(SVT_ENCDEC_STAGE_PAD);
     if (S.n_rec_pad) {
         rc = svt_hip_ref_pad_batch_device(ctx, S.n_rec_pad, S.rec_pad, pad_x, pad_y);
+        if (rc) return rc;
+    }
+    ED_STAGE(SVT_ENCDEC_STAGE_END);
+    return SVT_HIP_OK;
+}
+} // namespace
+
+extern "C" int32_t svt_hip_decode_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                               int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
+                                               int32_t *d_status) {
+    return decode_batch(ctx, w, n_pics, pics, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status, false);
+}
+
+/* the same pass for batches whose pictures may carry has_intra: step 3b runs for them (include/svtvp9_hip.h) */
+extern "C" int32_t svt_hip_decode_mixed_batch_device(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width,
+                                                     int32_t height, int32_t mi_stride, int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y,
+                                                     int32_t *d_status) {
+    return decode_batch(ctx, w, n_pics, pics, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status, true);
+}
+
+/* The decode twin of svt_hip_encdec_intra_device below: an intra picture rebuilt from its grid, coefficients and eob map by the
+ * coefficient-driven wavefront kernel (intra_recon_kernel.hip), then the same tail.  The eob map is an input (not cleared); d_nz is cleared
+ * and the kernel marks the units that hold coefficients, so svt_skip_update_kernel states the encode pass's rule (and a decoder's: a block
+ * whose transform blocks are all empty is skipped for the loop filter).  Everything is checked before the first enqueue: a refusal leaves
+ * every buffer as it was. */
+extern "C" int32_t svt_hip_decode_intra_device(svt_hip_ctx *ctx, svt_encdec_work *w, const svt_encdec_picture *pic, int32_t width, int32_t height, int32_t mi_stride,
+                                               int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y, int32_t *d_status) {
+    if (!ctx || !w || !pic || width != w->width || height != w->height || mi_stride < (width >> 3))
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: bad argument");
+    if (!d_status) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: null status");
+    const svt_encdec_picture &p = *pic;
+    if (!p.d_lf_mi || !p.recon.y || !p.recon.u || !p.recon.v || !p.d_qcoeff || !p.d_eob_map || !p.d_nz || (thr && !p.d_lfm))
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: null picture field");
+    if ((uintptr_t)p.d_qcoeff & 15) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: the coefficient array must be 16-byte aligned");
+    if (p.recon.y_stride > 65535 || ((p.recon.y_stride | p.recon.uv_stride) & 3) || (((uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v) & 3) ||
+        (p.pred.y && (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride) & 3)))
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: planes and strides must be 4-byte aligned");
+    if (p.pred.y && (!p.pred.u || !p.pred.v)) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: prediction planes");
+    svt_quant_tables qt[2];
+    if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: q index");
+    HIP_TRY(hipSetDevice(ctx->device));
+    ed_batch_dev hb;
+    memset(&hb, 0, sizeof hb);
+    fill_dims(hb, 1, width, height, mi_stride);
+    const uint32_t *offs = nullptr;
+    (void)svt_hip_vp9_iscan_tables(&offs, nullptr);
+    hb.pic[0].lf_mi = p.d_lf_mi; hb.pic[0].nz = p.d_nz; hb.pic[0].eob_map = p.d_eob_map; hb.pic[0].lfm = p.d_lfm;
+    const ed_batch_dev *dB = nullptr;
+    if (stage_batch(ctx, hb, &dB)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "decode_intra: descriptor buffers");
+    {
+        void *h = nullptr, *d = nullptr;
+        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "decode_intra: descriptor buffers");
+        memcpy(h, qt, sizeof qt);
+        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
+    }
+    HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
+    ED_STAGE(SVT_ENCDEC_STAGE_TQ);
+    HIP_TRY(hipMemsetAsync(p.d_nz, 0, (size_t)mi_stride * hb.mi_rows, ctx->stream));
+    int32_t rc = svt_intra_rc_launch(ctx, pic, width, height, mi_stride, w->d_qtabs, offs, w->d_intra_sync, w->d_status, (uint32_t *)d_status, 0);
+    if (rc) return rc;
+    ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
+    hipLaunchKernelGGL(svt_skip_update_kernel, dim3((hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
+    HIP_TRY(hipGetLastError());
+    ED_STAGE(SVT_ENCDEC_STAGE_LF);
+    svt_yuv_planes rec = p.recon;
+    rec.width = width; rec.height = height;
+    if (thr) {
+        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(hb.n_sb), dim3(64), 0, ctx->stream, dB, w->d_status);
+        HIP_TRY(hipGetLastError());
+        const svt_lf_mask *lfm = p.d_lfm;
+        const int32_t      lfm_stride = hb.sb_cols, mr = hb.mi_rows, mc = hb.mi_cols;
+        rc = svt_hip_lf_batch_device(ctx, 1, &rec, &lfm, &lfm_stride, thr, &mr, &mc, 0);
+        if (rc) return rc;
+    }
+    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
+    if (!p.no_pad) {
+        rc = svt_hip_ref_pad_batch_device(ctx, 1, &rec, pad_x, pad_y);
         if (rc) return rc;
     }
     ED_STAGE(SVT_ENCDEC_STAGE_END);

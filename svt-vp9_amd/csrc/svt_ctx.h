@@ -114,6 +114,10 @@ int32_t svt_rc_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_pred, uint
  * 16x16 luma cells) dwords of scratch */
 int32_t svt_intra_launch(svt_hip_ctx *ctx, const svt_encdec_picture *p, int32_t width, int32_t height, int32_t mi_stride, const svt_quant_tables *d_qtabs,
                          const int16_t *d_iscan, const uint32_t iscan_off[16], int32_t *d_sync, int32_t *d_status, int32_t mixed);
+/* decode pass of an intra picture's blocks (intra_recon_kernel.hip; used by encdec.hip): the same walk from coefficients and eobs.  d_sync as
+ * above; d_status_grid |= 1 for a malformed grid; d_overflow (may be null) += coefficients whose dequantised product left 16 bits */
+int32_t svt_intra_rc_launch(svt_hip_ctx *ctx, const svt_encdec_picture *p, int32_t width, int32_t height, int32_t mi_stride, const svt_quant_tables *d_qtabs,
+                            const uint32_t iscan_off[16], int32_t *d_sync, int32_t *d_status_grid, uint32_t *d_overflow, int32_t mixed);
 int32_t svt_md_intra_default_launch(svt_hip_ctx *ctx, svt_lf_mode_info *d_lf_mi, int32_t mi_stride, int32_t mi_rows, int32_t mi_cols, int32_t filter_level);
 
 #define HIP_TRY(expr)                                                        \
