@@ -312,22 +312,138 @@ struct ed_setup {
     int32_t             lfm_stride[ED_MAX_PICS], mi_rows_a[ED_MAX_PICS], mi_cols_a[ED_MAX_PICS];
 };
 
+/* an error under the name of the entry it belongs to: "encdec: ...", "decode: ...", "encdec_intra: ...", "decode_intra: ..." */
+int32_t ed_bad(const char *who, const char *what, int32_t code = SVT_HIP_ERR_BAD_PARAMETER) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return svt_set_error(code, msg);
+}
+
+/* quantiser tables of the q index -> the work area's pair */
+int32_t ed_send_qtabs(svt_hip_ctx *ctx, svt_encdec_work *w, const svt_quant_tables (&qt)[2], const char *who) {
+    void *h = nullptr, *d = nullptr;
+    if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return ed_bad(who, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
+    memcpy(h, qt, sizeof qt);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
+    return SVT_HIP_OK;
+}
+
+/* The stages the entries share.  Each is the launches of one step of a batch entry in their order; the entries keep the stage markers
+ * whose place differs between them (MC, LISTS, TQ, SKIP). */
+
+/* transform blocks from the grids: the lists of the batch in w->d_pos, their offsets and counts in w->d_off_cnt */
+int32_t ed_lists(svt_hip_ctx *ctx, svt_encdec_work *w, const ed_batch_dev &hb, const ed_batch_dev *dB) {
+    const int nwg = hb.n_pics * hb.n_sb;
+    hipLaunchKernelGGL(svt_tq_count_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_counts, w->d_status);
+    hipLaunchKernelGGL(svt_scan_sb_kernel, dim3(4 * hb.n_pics), dim3(256), 0, ctx->stream, w->d_counts, hb.n_sb, w->d_totals);
+    hipLaunchKernelGGL(svt_scan_pic_kernel, dim3(1), dim3(64), 0, ctx->stream, (const int32_t *)w->d_totals, hb.n_pics, w->d_bases, w->d_off_cnt);
+    hipLaunchKernelGGL(svt_tq_emit_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, (const int32_t *)w->d_counts, (const int32_t *)w->d_bases, (svt_tq_block *)nullptr, w->d_pos);
+    HIP_TRY(hipGetLastError());
+    if (!w->last_hb) w->last_hb = malloc(sizeof hb);
+    if (w->last_hb) memcpy(w->last_hb, &hb, sizeof hb);
+    return SVT_HIP_OK;
+}
+
+/* blocks of each transform size the batch holds at most */
+void ed_block_caps(const ed_batch_dev &hb, int32_t cap[4]) {
+    for (int s = 0; s < 4; s++) cap[s] = (int32_t)((size_t)hb.n_pics * hb.width * hb.height * 3 / 2 / (size_t)(16 << (2 * s)));
+}
+
+/* skip flags.  from_lists: the eob of every listed block goes to its picture's eob map and marks its unit first (the batch entries; the
+ * wavefront kernels of the intra entries have written both themselves) */
+int32_t ed_skip(svt_hip_ctx *ctx, svt_encdec_work *w, const ed_batch_dev &hb, const ed_batch_dev *dB, const bool from_lists) {
+    if (from_lists) {
+        const int total_cap = (int)(w->cap_per_pic * (size_t)hb.n_pics);
+        int       g = (total_cap + 255) / 256;
+        if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
+        hipLaunchKernelGGL(svt_tq_skip_kernel, dim3(g), dim3(256), 0, ctx->stream, dB, (const int32_t *)w->d_off_cnt, (const uint32_t *)w->d_pos, (const uint16_t *)w->d_eob);
+    }
+    hipLaunchKernelGGL(svt_skip_update_kernel, dim3((hb.n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
+    HIP_TRY(hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+/* loop-filter masks of n_pics pictures from their grids (status may be null) */
+int32_t ed_lf_masks(svt_hip_ctx *ctx, const ed_batch_dev *dB, int n_pics, int n_sb, int32_t *status) {
+    hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(n_pics * n_sb), dim3(64), 0, ctx->stream, dB, status);
+    HIP_TRY(hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+/* the tail of every entry: deblocking (thr = NULL: none) of the hb.n_pics pictures rec[], then the borders of rec_pad[0 .. n_rec_pad)
+ * (0: none), with the LF / PAD / END markers */
+int32_t ed_tail(svt_hip_ctx *ctx, svt_encdec_work *w, const ed_batch_dev &hb, const ed_batch_dev *dB, const svt_yuv_planes *rec, const svt_lf_mask *const *lfm,
+                const int32_t *lfm_stride, const int32_t *mi_rows_a, const int32_t *mi_cols_a, const svt_lf_thresh *thr, int n_rec_pad, const svt_yuv_planes *rec_pad,
+                int32_t pad_x, int32_t pad_y) {
+    ED_STAGE(SVT_ENCDEC_STAGE_LF);
+    if (thr) {
+        int32_t rc = ed_lf_masks(ctx, dB, hb.n_pics, hb.n_sb, w->d_status);
+        if (rc) return rc;
+        rc = svt_hip_lf_batch_device(ctx, hb.n_pics, rec, lfm, lfm_stride, thr, mi_rows_a, mi_cols_a, 0);
+        if (rc) return rc;
+    }
+    /* the reconstruction becomes a reference picture */
+    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
+    if (n_rec_pad) {
+        const int32_t rc = svt_hip_ref_pad_batch_device(ctx, n_rec_pad, rec_pad, pad_x, pad_y);
+        if (rc) return rc;
+    }
+    ED_STAGE(SVT_ENCDEC_STAGE_END);
+    return SVT_HIP_OK;
+}
+
+/* Set-up of svt_hip_encdec_intra_device (encode) and svt_hip_decode_intra_device: every refusal, then the one-picture parameter block and
+ * the q index's tables sent.  own_refusal: what the entry itself found wrong with its own arguments (null: nothing), reported behind
+ * "bad argument".  lf: the picture will be deblocked (d_lfm is needed).  Of the picture, src and d_dqcoeff are looked at for the encode
+ * entry only.  Everything is checked before the first enqueue: a refusal leaves every buffer as it was. */
+struct ed_intra_setup {
+    ed_batch_dev        hb;
+    const ed_batch_dev *dB;
+    const uint32_t     *iscan_off;
+    svt_yuv_planes      rec;
+    const svt_lf_mask  *lfm;
+    int32_t             lfm_stride, mi_rows, mi_cols;
+};
+int32_t ed_intra_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, const svt_encdec_picture *pic, int32_t width, int32_t height, int32_t mi_stride, int32_t q_index,
+                         const bool lf, const bool encode, const char *who, const char *own_refusal, ed_intra_setup &S) {
+    if (!ctx || !w || !pic || width != w->width || height != w->height || mi_stride < (width >> 3)) return ed_bad(who, "bad argument");
+    if (own_refusal) return ed_bad(who, own_refusal);
+    const svt_encdec_picture &p = *pic;
+    if (!p.d_lf_mi || (encode && (!p.src.y || !p.src.u || !p.src.v)) || !p.recon.y || !p.recon.u || !p.recon.v || !p.d_qcoeff || !p.d_eob_map || !p.d_nz || (lf && !p.d_lfm))
+        return ed_bad(who, "null picture field");
+    if (((uintptr_t)p.d_qcoeff | (encode ? (uintptr_t)p.d_dqcoeff : 0)) & 15)
+        return ed_bad(who, encode ? "coefficient arrays must be 16-byte aligned" : "the coefficient array must be 16-byte aligned");
+    if (p.recon.y_stride > 65535 || ((p.recon.y_stride | p.recon.uv_stride) & 3) || (((uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v) & 3) ||
+        (encode && (((p.src.y_stride | p.src.uv_stride) & 3) || (((uintptr_t)p.src.y | (uintptr_t)p.src.u | (uintptr_t)p.src.v) & 3))) ||
+        (p.pred.y && (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride) & 3)))
+        return ed_bad(who, "planes and strides must be 4-byte aligned");
+    if (p.pred.y && (!p.pred.u || !p.pred.v)) return ed_bad(who, "prediction planes");
+    svt_quant_tables qt[2];
+    if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return ed_bad(who, "q index");
+    HIP_TRY(hipSetDevice(ctx->device));
+    ed_batch_dev &hb = S.hb;
+    memset(&hb, 0, sizeof hb);
+    fill_dims(hb, 1, width, height, mi_stride);
+    (void)svt_hip_vp9_iscan_tables(&S.iscan_off, nullptr);
+    hb.pic[0].lf_mi = p.d_lf_mi; hb.pic[0].nz = p.d_nz; hb.pic[0].eob_map = p.d_eob_map; hb.pic[0].lfm = p.d_lfm;
+    if (stage_batch(ctx, hb, &S.dB)) return ed_bad(who, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
+    if (const int32_t e = ed_send_qtabs(ctx, w, qt, who)) return e;
+    /* what ed_tail takes: arrays of length 1 */
+    S.rec = p.recon; S.rec.width = width; S.rec.height = height;
+    S.lfm = p.d_lfm; S.lfm_stride = hb.sb_cols; S.mi_rows = hb.mi_rows; S.mi_cols = hb.mi_cols;
+    return SVT_HIP_OK;
+}
+
 /* Argument checking and descriptor set-up of svt_hip_encdec_batch_device and svt_hip_decode_batch_device: everything in front of the
  * first launch, the parameter block and the q index's tables sent.  decode: the pictures' src and d_dqcoeff are not looked at (the source
  * offsets of the geometry records read 0) and a picture with has_intra is refused unless allow_intra (svt_hip_decode_mixed_batch_device:
  * such a picture's planes and strides must then be 4-byte aligned, what the wavefront kernel's dword accesses need). */
-/* an error of ed_prepare under the name of the entry that called it: "encdec: ..." as before, "decode: ..." for the decode pass */
-int32_t ed_bad(bool decode, const char *what, int32_t code = SVT_HIP_ERR_BAD_PARAMETER) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "%s: %s", decode ? "decode" : "encdec", what);
-    return svt_set_error(code, msg);
-}
-
 int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const svt_encdec_picture *pics, int32_t width, int32_t height, int32_t mi_stride,
                    int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr, const bool decode, const bool allow_intra, ed_setup &S) {
+    const char *const who = decode ? "decode" : "encdec";
     if (!ctx || !w || !pics || !flags || n_pics < 1 || n_pics > w->max_pics || width != w->width || height != w->height || mi_stride < (width >> 3))
-        return ed_bad(decode, "bad argument");
-    if (flags->apply_loop_filter && !thr) return ed_bad(decode, "loop filter without thresholds");
+        return ed_bad(who, "bad argument");
+    if (flags->apply_loop_filter && !thr) return ed_bad(who, "loop filter without thresholds");
     if (decode && !allow_intra)
         for (int i = 0; i < n_pics; i++)
             if (pics[i].has_intra) return svt_set_error(SVT_HIP_ERR_UNSUPPORTED, "decode: pictures with intra blocks are not reconstructed by this entry");
@@ -338,13 +454,13 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
         const svt_encdec_picture &p = pics[i];
         if (!p.d_mc_mi || !p.d_lf_mi || (!decode && (!p.src.y || !p.src.u || !p.src.v)) || !p.pred.y || !p.pred.u || !p.pred.v || !p.recon.y || !p.recon.u || !p.recon.v ||
             !p.d_qcoeff || !p.d_eob_map || !p.d_nz || (flags->apply_loop_filter && !p.d_lfm))
-            return ed_bad(decode, "null picture field");
-        if (!decode && !p.d_dqcoeff != !pics[0].d_dqcoeff) return ed_bad(decode, "d_dqcoeff must be given for every picture of a batch or for none");
-        if (((uintptr_t)p.d_qcoeff | (decode ? 0 : (uintptr_t)p.d_dqcoeff)) & 15) return ed_bad(decode, "coefficient arrays must be 16-byte aligned");
+            return ed_bad(who, "null picture field");
+        if (!decode && !p.d_dqcoeff != !pics[0].d_dqcoeff) return ed_bad(who, "d_dqcoeff must be given for every picture of a batch or for none");
+        if (((uintptr_t)p.d_qcoeff | (decode ? 0 : (uintptr_t)p.d_dqcoeff)) & 15) return ed_bad(who, "coefficient arrays must be 16-byte aligned");
         if (decode && p.has_intra &&
             (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v |
               (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride | (uintptr_t)p.recon.y_stride | (uintptr_t)p.recon.uv_stride) & 3))
-            return ed_bad(decode, "planes and strides of a picture with intra blocks must be 4-byte aligned");
+            return ed_bad(who, "planes and strides of a picture with intra blocks must be 4-byte aligned");
         const uint8_t *s3[3] = {p.src.y, p.src.u, p.src.v}, *p3[3] = {p.pred.y, p.pred.u, p.pred.v};
         for (int k = 0; k < 3; k++) {
             if (!decode) { src_lo = (uintptr_t)s3[k] < src_lo ? (uintptr_t)s3[k] : src_lo; src_hi = (uintptr_t)s3[k] > src_hi ? (uintptr_t)s3[k] : src_hi; }
@@ -364,7 +480,7 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
         }
     }
     if ((uint64_t)(src_hi - src_lo) + plane_span >= (1ull << 32) || (uint64_t)(pred_hi - pred_lo) + plane_span >= (1ull << 32))
-        return ed_bad(decode, "the batch's source / prediction planes must lie within 4 GB");
+        return ed_bad(who, "the batch's source / prediction planes must lie within 4 GB");
     /* coefficient arrays: one base for the batch as well (element offsets are 32 bit) */
     uintptr_t q_lo = UINTPTR_MAX, dq_lo = UINTPTR_MAX;
     for (int i = 0; i < n_pics; i++) {
@@ -399,7 +515,7 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
             const int i = order[a];
             if (n_sets && (uint64_t)(hi[i] - (uintptr_t)recon_set[n_sets - 1]) + plane_span < (1ull << 32)) continue; /* (sorted: lo[i] >= the last base) */
             if (n_sets == ED_MAX_SETS || (uint64_t)(hi[i] - lo[i]) + plane_span >= (1ull << 32))
-                return ed_bad(decode, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
+                return ed_bad(who, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
             recon_set[n_sets++] = (uint8_t *)lo[i];
         }
     }
@@ -414,7 +530,7 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
         P.mc_mi = (svt_mc_mode_info *)p.d_mc_mi; P.lf_mi = p.d_lf_mi; P.nz = p.d_nz; P.eob_map = p.d_eob_map; P.lfm = p.d_lfm;
         const uintptr_t q_off = ((uintptr_t)p.d_qcoeff - q_lo) / sizeof(int16_t), dq_off = decode ? q_off : ((uintptr_t)p.d_dqcoeff - dq_lo) / sizeof(int16_t);
         if ((!decode && p.d_dqcoeff && q_off != dq_off) || q_off + (uint64_t)hb.n_sb * SVT_SB_COEFFS >= (1ull << 32))
-            return ed_bad(decode, "qcoeff / dqcoeff of the batch must be laid out alike, within 2^32 elements");
+            return ed_bad(who, "qcoeff / dqcoeff of the batch must be laid out alike, within 2^32 elements");
         /* the picture's reconstruction planes: 32-bit offsets from one of at most ED_MAX_SETS base pointers (a base serves every
            picture whose planes lie within 4 GB above it: buffers carved out of one slab share one) */
         const uint8_t *r3[3] = {p.recon.y, p.recon.u, p.recon.v};
@@ -423,14 +539,14 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
         int set = -1;
         for (int k = n_sets - 1; k >= 0 && set < 0; k--) /* the highest base at or below the picture: the one chosen for it above */
             if (r_lo >= (uintptr_t)recon_set[k] && (uint64_t)(r_hi - (uintptr_t)recon_set[k]) + plane_span < (1ull << 32)) set = k;
-        if (set < 0) return ed_bad(decode, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
+        if (set < 0) return ed_bad(who, "the batch's reconstruction buffers span more than 8 regions of 4 GB");
         svt_tq_pic_geom &g = P.g;
         const uint8_t *s3[3] = {p.src.y, p.src.u, p.src.v}, *p3[3] = {p.pred.y, p.pred.u, p.pred.v};
         for (int k = 0; k < 3; k++) {
             g.src_off[k] = decode ? 0u : (uint32_t)((uintptr_t)s3[k] - src_lo); g.pred_off[k] = (uint32_t)((uintptr_t)p3[k] - pred_lo);
             g.recon_off[k] = (uint32_t)((uintptr_t)r3[k] - (uintptr_t)recon_set[set]);
         }
-        if ((!decode && p.src.y_stride > 65535) || p.pred.y_stride > 65535 || p.recon.y_stride > 65535) return ed_bad(decode, "stride");
+        if ((!decode && p.src.y_stride > 65535) || p.pred.y_stride > 65535 || p.recon.y_stride > 65535) return ed_bad(who, "stride");
         g.src_stride[0] = decode ? 0 : (uint16_t)p.src.y_stride; g.src_stride[1] = decode ? 0 : (uint16_t)p.src.uv_stride;
         g.pred_stride[0] = (uint16_t)p.pred.y_stride; g.pred_stride[1] = (uint16_t)p.pred.uv_stride;
         g.recon_stride[0] = (uint16_t)p.recon.y_stride; g.recon_stride[1] = (uint16_t)p.recon.uv_stride;
@@ -442,16 +558,11 @@ int32_t ed_prepare(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const s
         lfm[i] = p.d_lfm; lfm_stride[i] = hb.sb_cols; mi_rows_a[i] = hb.mi_rows; mi_cols_a[i] = hb.mi_cols;
     }
     const ed_batch_dev *dB = nullptr;
-    if (stage_batch(ctx, hb, &dB)) return ed_bad(decode, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
+    if (stage_batch(ctx, hb, &dB)) return ed_bad(who, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
     /* quantiser tables of the q index */
-    {
-        svt_quant_tables qt[2];
-        if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return ed_bad(decode, "q index");
-        void *h = nullptr, *d = nullptr;
-        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return ed_bad(decode, "descriptor buffers", SVT_HIP_ERR_NO_RESOURCES);
-        memcpy(h, qt, sizeof qt);
-        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
-    }
+    svt_quant_tables qt[2];
+    if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return ed_bad(who, "q index");
+    if (const int32_t e = ed_send_qtabs(ctx, w, qt, who)) return e;
     S.dB = dB; S.src_lo = src_lo; S.pred_lo = pred_lo; S.q_lo = q_lo; S.dq_lo = dq_lo; S.n_sets = n_sets; S.n_rec_pad = n_rec_pad;
     return SVT_HIP_OK;
 }
@@ -467,29 +578,19 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
     const ed_batch_dev *dB = S.dB;
     const uintptr_t     src_lo = S.src_lo, pred_lo = S.pred_lo, q_lo = S.q_lo, dq_lo = S.dq_lo;
     uint8_t *const     *recon_set = S.recon_set;
-    const int           n_sets = S.n_sets, n_rec_pad = S.n_rec_pad;
-    const svt_mc_picture *mcp = S.mcp;
-    const svt_yuv_planes *rec = S.rec, *rec_pad = S.rec_pad;
-    const svt_lf_mask *const *lfm = S.lfm;
-    const int32_t      *lfm_stride = S.lfm_stride, *mi_rows_a = S.mi_rows_a, *mi_cols_a = S.mi_cols_a;
+    const int           n_sets = S.n_sets;
     /* 1. inter prediction of the whole batch */
     ED_STAGE(SVT_ENCDEC_STAGE_MC);
-    int32_t rc = svt_hip_inter_pred_batch_device(ctx, n_pics, mcp);
+    int32_t rc = svt_hip_inter_pred_batch_device(ctx, n_pics, S.mcp);
     if (rc) return rc;
     /* 2. transform blocks from the grids */
     ED_STAGE(SVT_ENCDEC_STAGE_LISTS);
-    const int nwg = n_pics * hb.n_sb;
-    hipLaunchKernelGGL(svt_tq_count_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_counts, w->d_status);
-    hipLaunchKernelGGL(svt_scan_sb_kernel, dim3(4 * n_pics), dim3(256), 0, ctx->stream, w->d_counts, hb.n_sb, w->d_totals);
-    hipLaunchKernelGGL(svt_scan_pic_kernel, dim3(1), dim3(64), 0, ctx->stream, (const int32_t *)w->d_totals, n_pics, w->d_bases, w->d_off_cnt);
-    hipLaunchKernelGGL(svt_tq_emit_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, (const int32_t *)w->d_counts, (const int32_t *)w->d_bases, (svt_tq_block *)nullptr, w->d_pos);
-    HIP_TRY(hipGetLastError());
-    if (!w->last_hb) w->last_hb = malloc(sizeof hb);
-    if (w->last_hb) memcpy(w->last_hb, &hb, sizeof hb);
+    rc = ed_lists(ctx, w, hb, dB);
+    if (rc) return rc;
     /* 3. residual -> transform -> quantisation (-> inverse -> reconstruction) */
     ED_STAGE(SVT_ENCDEC_STAGE_TQ);
     int32_t cap[4];
-    for (int s = 0; s < 4; s++) cap[s] = (int32_t)((size_t)n_pics * width * height * 3 / 2 / (size_t)(16 << (2 * s)));
+    ed_block_caps(hb, cap);
     rc = svt_tq_launch_device_lists(ctx, (const uint8_t *)src_lo, (const uint8_t *)pred_lo, recon_set, n_sets, nullptr, cap, w->d_off_cnt, w->d_qtabs, w->d_iscan,
                                     (int16_t *)q_lo, (int16_t *)dq_lo, w->d_eob, nullptr, w->d_pos, &dB->pic[0].g, (int)sizeof(ed_pic_dev), dB->iscan_off, hb.sb_cols);
     if (rc) return rc;
@@ -512,30 +613,11 @@ extern "C" int32_t svt_hip_encdec_batch_device(svt_hip_ctx *ctx, svt_encdec_work
             rc = svt_intra_launch(ctx, &pics[i], width, height, mi_stride, w->d_qtabs, w->d_iscan, hb.iscan_off, w->d_intra_sync, w->d_status, 1);
             if (rc) return rc;
         }
-    {
-        const int total_cap = (int)(w->cap_per_pic * (size_t)n_pics);
-        int       g = (total_cap + 255) / 256;
-        if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
-        hipLaunchKernelGGL(svt_tq_skip_kernel, dim3(g), dim3(256), 0, ctx->stream, dB, (const int32_t *)w->d_off_cnt, (const uint32_t *)w->d_pos, (const uint16_t *)w->d_eob);
-        hipLaunchKernelGGL(svt_skip_update_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
-        HIP_TRY(hipGetLastError());
-    }
-    /* 5. deblocking */
-    ED_STAGE(SVT_ENCDEC_STAGE_LF);
-    if (flags->apply_loop_filter) {
-        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_status);
-        HIP_TRY(hipGetLastError());
-        rc = svt_hip_lf_batch_device(ctx, n_pics, rec, lfm, lfm_stride, thr, mi_rows_a, mi_cols_a, 0);
-        if (rc) return rc;
-    }
-    /* 6. the reconstruction becomes a reference picture */
-    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
-    if (flags->pad_reference && n_rec_pad) {
-        rc = svt_hip_ref_pad_batch_device(ctx, n_rec_pad, rec_pad, pad_x, pad_y);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_END);
-    return SVT_HIP_OK;
+    rc = ed_skip(ctx, w, hb, dB, true);
+    if (rc) return rc;
+    /* 5. deblocking, 6. the reconstruction becomes a reference picture */
+    return ed_tail(ctx, w, hb, dB, S.rec, S.lfm, S.lfm_stride, S.mi_rows_a, S.mi_cols_a, flags->apply_loop_filter ? thr : nullptr, flags->pad_reference ? S.n_rec_pad : 0,
+                   S.rec_pad, pad_x, pad_y);
 }
 
 namespace {
@@ -574,19 +656,14 @@ int32_t decode_batch(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const
     if (rc) return rc;
     /* 2. transform blocks from the grids */
     ED_STAGE(SVT_ENCDEC_STAGE_LISTS);
-    const int nwg = n_pics * hb.n_sb;
-    hipLaunchKernelGGL(svt_tq_count_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_counts, w->d_status);
-    hipLaunchKernelGGL(svt_scan_sb_kernel, dim3(4 * n_pics), dim3(256), 0, ctx->stream, w->d_counts, hb.n_sb, w->d_totals);
-    hipLaunchKernelGGL(svt_scan_pic_kernel, dim3(1), dim3(64), 0, ctx->stream, (const int32_t *)w->d_totals, n_pics, w->d_bases, w->d_off_cnt);
-    hipLaunchKernelGGL(svt_tq_emit_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, (const int32_t *)w->d_counts, (const int32_t *)w->d_bases, (svt_tq_block *)nullptr, w->d_pos);
+    rc = ed_lists(ctx, w, hb, dB);
+    if (rc) return rc;
     hipLaunchKernelGGL(svt_dec_intra_check_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB, w->d_status, intra_mask);
     HIP_TRY(hipGetLastError());
-    if (!w->last_hb) w->last_hb = malloc(sizeof hb);
-    if (w->last_hb) memcpy(w->last_hb, &hb, sizeof hb);
     /* 3. coefficients -> dequantisation -> inverse transform -> reconstruction; d_status[0] = coefficients that overflowed 16 bits */
     ED_STAGE(SVT_ENCDEC_STAGE_TQ);
     int32_t cap[4];
-    for (int s = 0; s < 4; s++) cap[s] = (int32_t)((size_t)n_pics * width * height * 3 / 2 / (size_t)(16 << (2 * s)));
+    ed_block_caps(hb, cap);
     rc = svt_rc_launch_device_lists(ctx, (const uint8_t *)S.pred_lo, S.recon_set, S.n_sets, cap, w->d_off_cnt, w->d_qtabs, (const int16_t *)S.q_lo, w->d_eob, w->d_pos,
                                     &dB->pic[0].g, &dB->pic[0].eob_map, (int)sizeof(ed_pic_dev), dB->iscan_off, hb.sb_cols, (uint32_t *)d_status);
     if (rc) return rc;
@@ -599,30 +676,10 @@ int32_t decode_batch(svt_hip_ctx *ctx, svt_encdec_work *w, int32_t n_pics, const
         }
     /* 4. skip flags from the eobs (above) */
     ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
-    {
-        const int total_cap = (int)(w->cap_per_pic * (size_t)n_pics);
-        int       g = (total_cap + 255) / 256;
-        if (g > ctx->cu_count * 8) g = ctx->cu_count * 8;
-        hipLaunchKernelGGL(svt_tq_skip_kernel, dim3(g), dim3(256), 0, ctx->stream, dB, (const int32_t *)w->d_off_cnt, (const uint32_t *)w->d_pos, (const uint16_t *)w->d_eob);
-        hipLaunchKernelGGL(svt_skip_update_kernel, dim3((n_pics * hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
-        HIP_TRY(hipGetLastError());
-    }
-    /* 5. deblocking (thr = NULL: the header's filter level is 0) */
-    ED_STAGE(SVT_ENCDEC_STAGE_LF);
-    if (thr) {
-        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(nwg), dim3(64), 0, ctx->stream, dB, w->d_status);
-        HIP_TRY(hipGetLastError());
-        rc = svt_hip_lf_batch_device(ctx, n_pics, S.rec, S.lfm, S.lfm_stride, thr, S.mi_rows_a, S.mi_cols_a, 0);
-        if (rc) return rc;
-    }
-    /* 6. the reconstruction becomes a reference picture */
-    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
-    if (S.n_rec_pad) {
-        rc = svt_hip_ref_pad_batch_device(ctx, S.n_rec_pad, S.rec_pad, pad_x, pad_y);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_END);
-    return SVT_HIP_OK;
+    rc = ed_skip(ctx, w, hb, dB, true);
+    if (rc) return rc;
+    /* 5. deblocking (thr = NULL: the header's filter level is 0), 6. the reconstruction becomes a reference picture */
+    return ed_tail(ctx, w, hb, dB, S.rec, S.lfm, S.lfm_stride, S.mi_rows_a, S.mi_cols_a, thr, S.n_rec_pad, S.rec_pad, pad_x, pad_y);
 }
 } // namespace
 
@@ -646,123 +703,37 @@ extern "C" int32_t svt_hip_decode_mixed_batch_device(svt_hip_ctx *ctx, svt_encde
  * every buffer as it was. */
 extern "C" int32_t svt_hip_decode_intra_device(svt_hip_ctx *ctx, svt_encdec_work *w, const svt_encdec_picture *pic, int32_t width, int32_t height, int32_t mi_stride,
                                                int32_t q_index, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y, int32_t *d_status) {
-    if (!ctx || !w || !pic || width != w->width || height != w->height || mi_stride < (width >> 3))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: bad argument");
-    if (!d_status) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: null status");
-    const svt_encdec_picture &p = *pic;
-    if (!p.d_lf_mi || !p.recon.y || !p.recon.u || !p.recon.v || !p.d_qcoeff || !p.d_eob_map || !p.d_nz || (thr && !p.d_lfm))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: null picture field");
-    if ((uintptr_t)p.d_qcoeff & 15) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: the coefficient array must be 16-byte aligned");
-    if (p.recon.y_stride > 65535 || ((p.recon.y_stride | p.recon.uv_stride) & 3) || (((uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v) & 3) ||
-        (p.pred.y && (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride) & 3)))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: planes and strides must be 4-byte aligned");
-    if (p.pred.y && (!p.pred.u || !p.pred.v)) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: prediction planes");
-    svt_quant_tables qt[2];
-    if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "decode_intra: q index");
-    HIP_TRY(hipSetDevice(ctx->device));
-    ed_batch_dev hb;
-    memset(&hb, 0, sizeof hb);
-    fill_dims(hb, 1, width, height, mi_stride);
-    const uint32_t *offs = nullptr;
-    (void)svt_hip_vp9_iscan_tables(&offs, nullptr);
-    hb.pic[0].lf_mi = p.d_lf_mi; hb.pic[0].nz = p.d_nz; hb.pic[0].eob_map = p.d_eob_map; hb.pic[0].lfm = p.d_lfm;
-    const ed_batch_dev *dB = nullptr;
-    if (stage_batch(ctx, hb, &dB)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "decode_intra: descriptor buffers");
-    {
-        void *h = nullptr, *d = nullptr;
-        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "decode_intra: descriptor buffers");
-        memcpy(h, qt, sizeof qt);
-        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
-    }
+    ed_intra_setup S;
+    if (const int32_t e = ed_intra_prepare(ctx, w, pic, width, height, mi_stride, q_index, thr != nullptr, false, "decode_intra", d_status ? nullptr : "null status", S)) return e;
     HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int32_t), ctx->stream));
     ED_STAGE(SVT_ENCDEC_STAGE_TQ);
-    HIP_TRY(hipMemsetAsync(p.d_nz, 0, (size_t)mi_stride * hb.mi_rows, ctx->stream));
-    int32_t rc = svt_intra_rc_launch(ctx, pic, width, height, mi_stride, w->d_qtabs, offs, w->d_intra_sync, w->d_status, (uint32_t *)d_status, 0);
+    HIP_TRY(hipMemsetAsync(pic->d_nz, 0, (size_t)mi_stride * S.hb.mi_rows, ctx->stream));
+    int32_t rc = svt_intra_rc_launch(ctx, pic, width, height, mi_stride, w->d_qtabs, S.iscan_off, w->d_intra_sync, w->d_status, (uint32_t *)d_status, 0);
     if (rc) return rc;
     ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
-    hipLaunchKernelGGL(svt_skip_update_kernel, dim3((hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
-    HIP_TRY(hipGetLastError());
-    ED_STAGE(SVT_ENCDEC_STAGE_LF);
-    svt_yuv_planes rec = p.recon;
-    rec.width = width; rec.height = height;
-    if (thr) {
-        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(hb.n_sb), dim3(64), 0, ctx->stream, dB, w->d_status);
-        HIP_TRY(hipGetLastError());
-        const svt_lf_mask *lfm = p.d_lfm;
-        const int32_t      lfm_stride = hb.sb_cols, mr = hb.mi_rows, mc = hb.mi_cols;
-        rc = svt_hip_lf_batch_device(ctx, 1, &rec, &lfm, &lfm_stride, thr, &mr, &mc, 0);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
-    if (!p.no_pad) {
-        rc = svt_hip_ref_pad_batch_device(ctx, 1, &rec, pad_x, pad_y);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_END);
-    return SVT_HIP_OK;
+    rc = ed_skip(ctx, w, S.hb, S.dB, false);
+    if (rc) return rc;
+    return ed_tail(ctx, w, S.hb, S.dB, &S.rec, &S.lfm, &S.lfm_stride, &S.mi_rows, &S.mi_cols, thr, pic->no_pad ? 0 : 1, &S.rec, pad_x, pad_y);
 }
 
 /* An intra picture: prediction + transform + reconstruction by the wavefront kernel (intra_kernel.hip), then the same tail as a batch of
  * inter pictures -- skip flags, loop-filter masks, deblocking, border. */
 extern "C" int32_t svt_hip_encdec_intra_device(svt_hip_ctx *ctx, svt_encdec_work *w, const svt_encdec_picture *pic, int32_t width, int32_t height, int32_t mi_stride,
                                                int32_t q_index, const svt_encdec_flags *flags, const svt_lf_thresh *thr, int32_t pad_x, int32_t pad_y) {
-    if (!ctx || !w || !pic || !flags || width != w->width || height != w->height || mi_stride < (width >> 3))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: bad argument");
-    if (!flags->do_recon) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: intra prediction needs the reconstruction (do_recon)");
-    if (flags->apply_loop_filter && !thr) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: loop filter without thresholds");
-    const svt_encdec_picture &p = *pic;
-    if (!p.d_lf_mi || !p.src.y || !p.src.u || !p.src.v || !p.recon.y || !p.recon.u || !p.recon.v || !p.d_qcoeff || !p.d_eob_map || !p.d_nz ||
-        (flags->apply_loop_filter && !p.d_lfm))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: null picture field");
-    if (((uintptr_t)p.d_qcoeff | (uintptr_t)p.d_dqcoeff) & 15) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: coefficient arrays must be 16-byte aligned");
-    if (p.recon.y_stride > 65535 || ((p.src.y_stride | p.src.uv_stride | p.recon.y_stride | p.recon.uv_stride) & 3) ||
-        (((uintptr_t)p.src.y | (uintptr_t)p.src.u | (uintptr_t)p.src.v | (uintptr_t)p.recon.y | (uintptr_t)p.recon.u | (uintptr_t)p.recon.v) & 3) ||
-        (p.pred.y && (((uintptr_t)p.pred.y | (uintptr_t)p.pred.u | (uintptr_t)p.pred.v | (uintptr_t)p.pred.y_stride | (uintptr_t)p.pred.uv_stride) & 3)))
-        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: planes and strides must be 4-byte aligned");
-    if (p.pred.y && (!p.pred.u || !p.pred.v)) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: prediction planes");
-    HIP_TRY(hipSetDevice(ctx->device));
-    ed_batch_dev hb;
-    memset(&hb, 0, sizeof hb);
-    fill_dims(hb, 1, width, height, mi_stride);
-    const uint32_t *offs = nullptr;
-    (void)svt_hip_vp9_iscan_tables(&offs, nullptr);
-    hb.pic[0].lf_mi = p.d_lf_mi; hb.pic[0].nz = p.d_nz; hb.pic[0].eob_map = p.d_eob_map; hb.pic[0].lfm = p.d_lfm;
-    const ed_batch_dev *dB = nullptr;
-    if (stage_batch(ctx, hb, &dB)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec_intra: descriptor buffers");
-    {
-        svt_quant_tables qt[2];
-        if (svt_hip_quant_tables_for_qindex(q_index, qt) != SVT_HIP_OK) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "encdec_intra: q index");
-        void *h = nullptr, *d = nullptr;
-        if (svt_ctx_stage(ctx, sizeof qt, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "encdec_intra: descriptor buffers");
-        memcpy(h, qt, sizeof qt);
-        HIP_TRY(svt_ctx_stage_send(ctx, sizeof qt, w->d_qtabs)); /* (the work area's tables, not the slot's device twin) */
-    }
+    const char *const own = !flags ? "bad argument" : !flags->do_recon ? "intra prediction needs the reconstruction (do_recon)" :
+                            flags->apply_loop_filter && !thr ? "loop filter without thresholds" : nullptr;
+    ed_intra_setup S;
+    if (const int32_t e = ed_intra_prepare(ctx, w, pic, width, height, mi_stride, q_index, flags && flags->apply_loop_filter, true, "encdec_intra", own, S)) return e;
     ED_STAGE(SVT_ENCDEC_STAGE_TQ);
-    HIP_TRY(hipMemsetAsync(p.d_eob_map, 0, (size_t)(width / 4) * (height / 4) * 3 / 2 * sizeof(uint16_t), ctx->stream));
-    HIP_TRY(hipMemsetAsync(p.d_nz, 0, (size_t)mi_stride * hb.mi_rows, ctx->stream));
-    int32_t rc = svt_intra_launch(ctx, pic, width, height, mi_stride, w->d_qtabs, w->d_iscan, offs, w->d_intra_sync, w->d_status, 0);
+    HIP_TRY(hipMemsetAsync(pic->d_eob_map, 0, (size_t)(width / 4) * (height / 4) * 3 / 2 * sizeof(uint16_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(pic->d_nz, 0, (size_t)mi_stride * S.hb.mi_rows, ctx->stream));
+    int32_t rc = svt_intra_launch(ctx, pic, width, height, mi_stride, w->d_qtabs, w->d_iscan, S.iscan_off, w->d_intra_sync, w->d_status, 0);
     if (rc) return rc;
     ED_STAGE(SVT_ENCDEC_STAGE_SKIP);
-    hipLaunchKernelGGL(svt_skip_update_kernel, dim3((hb.mi_rows * hb.mi_cols + 255) / 256), dim3(256), 0, ctx->stream, dB);
-    HIP_TRY(hipGetLastError());
-    ED_STAGE(SVT_ENCDEC_STAGE_LF);
-    svt_yuv_planes rec = p.recon;
-    rec.width = width; rec.height = height;
-    if (flags->apply_loop_filter) {
-        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(hb.n_sb), dim3(64), 0, ctx->stream, dB, w->d_status);
-        HIP_TRY(hipGetLastError());
-        const svt_lf_mask *lfm = p.d_lfm;
-        const int32_t      lfm_stride = hb.sb_cols, mr = hb.mi_rows, mc = hb.mi_cols;
-        rc = svt_hip_lf_batch_device(ctx, 1, &rec, &lfm, &lfm_stride, thr, &mr, &mc, 0);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_PAD);
-    if (flags->pad_reference && !p.no_pad) {
-        rc = svt_hip_ref_pad_batch_device(ctx, 1, &rec, pad_x, pad_y);
-        if (rc) return rc;
-    }
-    ED_STAGE(SVT_ENCDEC_STAGE_END);
-    return SVT_HIP_OK;
+    rc = ed_skip(ctx, w, S.hb, S.dB, false);
+    if (rc) return rc;
+    return ed_tail(ctx, w, S.hb, S.dB, &S.rec, &S.lfm, &S.lfm_stride, &S.mi_rows, &S.mi_cols, flags->apply_loop_filter ? thr : nullptr,
+                   flags->pad_reference && !pic->no_pad ? 1 : 0, &S.rec, pad_x, pad_y);
 }
 
 extern "C" int32_t svt_hip_md_intra_default_device(svt_hip_ctx *ctx, int32_t width, int32_t height, int32_t filter_level, svt_lf_mode_info *d_lf_mi, int32_t mi_stride) {
@@ -857,8 +828,7 @@ extern "C" int32_t svt_hip_lf_build_masks_device(svt_hip_ctx *ctx, int32_t n_pic
         }
         const ed_batch_dev *dB = nullptr;
         if (stage_batch(ctx, hb, &dB)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "lf_masks: descriptor buffers");
-        hipLaunchKernelGGL(svt_lf_mask_kernel, dim3(n * hb.n_sb), dim3(64), 0, ctx->stream, dB, (int32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
+        if (const int32_t e = ed_lf_masks(ctx, dB, n, hb.n_sb, nullptr)) return e;
     }
     return SVT_HIP_OK;
 }
