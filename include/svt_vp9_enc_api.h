@@ -122,7 +122,9 @@ typedef struct svt_vp9_shim_picture_info {
     int32_t  is_used_as_reference, do_recon, apply_loop_filter, pad_reference;
     int32_t  q_index, filter_level;
     int32_t  decision_source;      /* 0 built-in stand-in, 1 the host's callback, 2 the searched intra stand-in (an intra picture no callback
-                                      decided, with SVT_HIP_INTRA_DECISION=search: svt_hip_intra_search_device + svt_hip_md_intra_search_device) */
+                                      decided, with SVT_HIP_INTRA_DECISION=search: svt_hip_intra_search_device + svt_hip_md_intra_search_device),
+                                      3 the mixed inter stand-in (an inter picture no callback decided, with SVT_HIP_INTER_DECISION=mixed:
+                                      svt_hip_intra_search_batch_device + svt_hip_md_mixed_batch_device; the picture may hold intra leaves) */
     int32_t  intra_recon_is_source; /* always 0 since round 4: intra pictures go through the intra encode pass on the GPU
                                       (svt_hip_encdec_intra_device); the field keeps the struct layout of round 3 */
     int32_t  device_ordinal;       /* the GPU that coded the picture's GOP */
@@ -159,7 +161,15 @@ EbErrorType svt_vp9_shim_get_counters(EbComponentType *svt_enc_component, uint64
  * ac quantiser step, the key-frame filter level; decision_source 2); any other value makes eb_vp9_init_encoder fail with
  * EB_ErrorBadParameter.  The grids of an INTER picture may hold intra blocks as well (is_inter 0 + modes in
  * lf_mode_info, ref_list[0] = -1 in mc_mode_info) as long as the picture is reconstructed (info->do_recon; the reference's limit_intra
- * forbids intra blocks in the others): they are coded from their neighbours' reconstruction behind the inter blocks. */
+ * forbids intra blocks in the others): they are coded from their neighbours' reconstruction behind the inter blocks.
+ * The environment variable SVT_HIP_INTER_DECISION, read by eb_vp9_init_encoder for that encoder, chooses the stand-in of an INTER picture
+ * no callback decided: unset or "default" as above (every block inter); "mixed" = the mixed stand-in of svtvp9_hip.h
+ * (svt_hip_md_mixed_batch_device): the open-loop intra search of the picture's source without its 4x4 blocks, then the default
+ * partition over min(ME distortion, intra luma SAD + intra_penalty) per block, a leaf intra where its intra side is strictly smaller;
+ * lambda = 4 x the ac quantiser step of the picture's q index as for the default, intra_penalty = 2 lambda -- an untuned stand-in value,
+ * not a claim of coding efficiency; decision_source 3.  A wave of pictures that came out with intra leaves is reconstructed like a wave
+ * whose callback put intra blocks into it.  The opt-in makes the library wait for the intra-unit counts of every wave and costs the
+ * search; any other value makes eb_vp9_init_encoder fail with EB_ErrorBadParameter. */
 typedef int32_t (*svt_vp9_shim_md_callback)(void *user, const svt_vp9_shim_picture_info *info, const void *me_results, void *mc_mode_info,
                                             void *lf_mode_info, int32_t mi_stride);
 EbErrorType svt_vp9_shim_set_mode_decision(EbComponentType *svt_enc_component, svt_vp9_shim_md_callback callback, void *user);

@@ -1329,6 +1329,12 @@ typedef struct svt_ois_block {   /* 12 bytes */
 /* d_out: n_sb * SVT_OIS_PER_SB records, SB raster order (device memory).  src: device planes (luma stride >= width, chroma stride >=
  * width / 2).  Width and height multiples of 8.  Asynchronous on the context's stream. */
 int32_t svt_hip_intra_search_device(svt_hip_ctx *ctx, const svt_yuv_planes *src, int32_t width, int32_t height, svt_ois_block *d_out);
+/* The same for n_pics pictures of one geometry in one launch (srcs, d_out: host arrays of n_pics entries holding device pointers).  With
+ * with_4x4 = 1 every picture's records equal svt_hip_intra_search_device's.  with_4x4 = 0 leaves the 256 luma 4x4 blocks of an SB out:
+ * records 0 .. 83 are the same, records 84 .. 339 are written as "none" (sad = uv_sad = UINT32_MAX, mode = uv_mode = 0xFF).  A null plane
+ * or output, a stride below the width, a misaligned output or with_4x4 outside {0, 1}: SVT_HIP_ERR_BAD_PARAMETER, nothing launched. */
+int32_t svt_hip_intra_search_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_yuv_planes *srcs, int32_t width, int32_t height, int32_t with_4x4,
+                                          svt_ois_block *const *d_out);
 /* Stand-in intra decision from the OIS records (NOT the reference's mode decision): cost of a coded block J = D + lambda, D = sad +
  * uv_sad for blocks >= 8x8, and for a unit of four 4x4 blocks (sb_type 0) the sum of the four 4x4 sad + the 8x8 record's uv_sad.
  * Bottom-up: 8x8 against its four 4x4 blocks, 16x16 against its four best 8x8 subtrees, 32x32 against its four best 16x16 subtrees;
@@ -1371,6 +1377,36 @@ int32_t svt_hip_md_default_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const 
                                         int32_t mi_stride);
 int32_t svt_hip_md_default_picture(const svt_me_pu_result *results, int32_t pic_width, int32_t pic_height, uint32_t lambda, int32_t filter_level,
                                    svt_mc_mode_info *mc_mi, svt_lf_mode_info *lf_mi, int32_t mi_stride);
+
+/* Mixed stand-in for mode decision of an inter picture (NOT the reference's either; deterministic, no claim of coding efficiency): the
+ * partition of svt_hip_md_default_batch_device with an intra alternative per PU, from the ME records and the records of the open-loop
+ * intra search of the same picture.  PU p of an SB: 0 the 64x64, 1..4 the 32x32, 5..20 the 16x16, 21..84 the 8x8 blocks, each group in
+ * z-order -- the order of the OIS groups too, so the OIS record of PU p >= 1 is record p - 1 of the SB.
+ *      inter(p) = results[p].distortion_direction[0].distortion
+ *      intra(p) = ois[p - 1].sad + intra_penalty (64 bits); none where the record's sad is UINT32_MAX, and for the 64x64 PU
+ *      cost(p)  = min(inter(p), intra(p))
+ * Only luma SADs are compared (ME's distortion is luma only; uv_sad takes no part).  The bottom-up merge is the default stand-in's with
+ * cost(p) in place of the ME distortion (parent when cost(parent) <= sum cost(children) + 3 lambda; split at the picture edge down to
+ * 8x8).  A leaf is intra iff intra(p) < inter(p): ties go to inter.  No unit of four 4x4 blocks is produced; records 84 .. 339 of an SB are
+ * not read, so the batched search may leave its 4x4 phase out.  An inter leaf is written as the default stand-in writes it.  An intra
+ * leaf: sb_type 3 / 6 / 9, tx_size 1 / 2 / 3, is_inter = skip = 0, pad_[0] = 0, pad_[1] / pad_[2] = the record's mode / uv_mode; in the
+ * prediction grid bw8 = bh8 = its size, ref_list = {-1, -1}, vectors 0.  With intra_penalty >= 1 << 24 (a 64x64 SAD is at most
+ * 64 * 64 * 255) no leaf of real ME records is intra and both grids equal the default stand-in's byte for byte.
+ * d_intra_units[i] (n_pics counters in device memory) = number of 8x8 units of picture i written with is_inter = 0; the entry zeroes them
+ * on the stream first.  A caller derives svt_encdec_picture.has_intra from it.  Pictures are host records of device pointers; d_results
+ * and d_ois 4-byte aligned.  A null field, a misaligned pointer or a bad size: SVT_HIP_ERR_BAD_PARAMETER, nothing launched or written.
+ * svt_hip_md_mixed_picture is the host form (same text, csrc/encdec_core.h); *intra_units receives the count. */
+typedef struct svt_md_mixed_picture {
+    const svt_me_pu_result *d_results;  /* n_sb * 85 */
+    const svt_ois_block    *d_ois;      /* n_sb * SVT_OIS_PER_SB */
+    svt_mc_mode_info       *d_mc_mi;
+    svt_lf_mode_info       *d_lf_mi;
+} svt_md_mixed_picture;
+int32_t svt_hip_md_mixed_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_md_mixed_picture *pics, int32_t width, int32_t height, uint32_t lambda,
+                                      uint32_t intra_penalty, int32_t filter_level, int32_t mi_stride, int32_t *d_intra_units);
+int32_t svt_hip_md_mixed_picture(const svt_me_pu_result *results, const svt_ois_block *ois, int32_t pic_width, int32_t pic_height, uint32_t lambda,
+                                 uint32_t intra_penalty, int32_t filter_level, svt_mc_mode_info *mc_mi, svt_lf_mode_info *lf_mi, int32_t mi_stride,
+                                 int32_t *intra_units);
 
 /* device form of svt_hip_lf_build_masks (same text): masks of n_pics pictures from device-resident grids */
 int32_t svt_hip_lf_build_masks_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_lf_mode_info *const *d_lf_mi, int32_t mi_stride, int32_t mi_rows,

@@ -275,6 +275,10 @@ assert OIS_BLOCK_DTYPE.itemsize == 12
 OIS_PER_SB = 340
 OIS_NONE = 0xFFFFFFFF
 
+
+class MdMixedPicture(C.Structure):  # svt_md_mixed_picture: device pointers of one picture of svt_hip_md_mixed_batch_device
+    _fields_ = [("d_results", C.c_void_p), ("d_ois", C.c_void_p), ("d_mc_mi", C.c_void_p), ("d_lf_mi", C.c_void_p)]
+
 # every symbol include/svtvp9_hip.h declares
 EXPORTS = [
     "svt_hip_sb_count", "svt_hip_input_resolution", "svt_hip_me_params_derive", "svt_hip_me_params_preset", "svt_hip_ctx_create", "svt_hip_ctx_create_on_stream", "svt_hip_ctx_create_cu_mask", "svt_hip_ctx_stream",
@@ -296,6 +300,7 @@ EXPORTS = [
     "svt_hip_mem_download_2d_async", "svt_hip_mem_copy_2d_device", "svt_hip_encdec_work_set_stage_hook", "svt_hip_me_params_same_launch", "svt_hip_me_kernel_instance", "svt_hip_ctx_set_intra_workgroups", "svt_hip_ctx_warm", "svt_hip_ctx_warm_scratch", "svt_hip_lf_reserve",
     "svt_hip_me_last_instance", "svt_hip_me_lds_bytes", "svt_hip_vp9_layer_qindex", "svt_hip_mem_upload_2d_direct", "svt_hip_mem_upload_wait", "svt_hip_host_unregister_all", "svt_hip_host_registry_retain", "svt_hip_host_registry_release",
     "svt_hip_intra_search_device", "svt_hip_md_intra_search_device", "svt_hip_md_intra_search_picture",
+    "svt_hip_intra_search_batch_device", "svt_hip_md_mixed_batch_device", "svt_hip_md_mixed_picture",
     "svt_hip_pa_noise_params_derive", "svt_hip_pa_noise_batch_device", "svt_hip_pa_histogram_batch_device", "svt_hip_pa_chroma_mean_batch_device",
     "svt_hip_vp9_scan_tables", "svt_hip_tokenize_blocks_device", "svt_hip_tokenize_blocks", "svt_hip_tokenize_blocks_host", "svt_hip_tokenize_batch_device", "svt_hip_tokenize_picture",
     "svt_hip_tokenize_capacity",
@@ -368,6 +373,12 @@ def load():
         _lib.svt_hip_decode_mixed_batch_device.argtypes = _lib.svt_hip_decode_batch_device.argtypes
         # (ctx, work, pic, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status)
         _lib.svt_hip_decode_intra_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        # (ctx, n_pics, pics, width, height, lambda, intra_penalty, filter_level, mi_stride, d_intra_units)
+        _lib.svt_hip_md_mixed_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _u32, _u32, C.c_int32, C.c_int32, C.c_void_p]
+        # (results, ois, width, height, lambda, intra_penalty, filter_level, mc_mi, lf_mi, mi_stride, intra_units)
+        _lib.svt_hip_md_mixed_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _u32, _u32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        # (ctx, n_pics, srcs, width, height, with_4x4, d_out)
+        _lib.svt_hip_intra_search_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     return _lib
 
 

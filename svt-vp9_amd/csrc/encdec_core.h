@@ -14,6 +14,8 @@
  *                            without a host-supplied decision
  *   svt_md_intra_search_unit the intra counterpart (NOT the reference's either): the records of the open-loop intra search
  *                            (svt_ois_block) -> a grid of intra blocks 4x4 .. 32x32 with their modes
+ *   svt_md_mixed_unit        the two together for an inter picture (NOT the reference's): svt_md_default_unit's partition over
+ *                            min(ME distortion, OIS luma SAD + penalty) per PU; a leaf whose intra side is smaller is an intra block
  */
 #ifndef SVT_ENCDEC_CORE_H
 #define SVT_ENCDEC_CORE_H
@@ -361,6 +363,71 @@ SVT_HD void svt_md_intra_search_unit(const svt_ois_block *ois, int r, int c, int
         lf->pad_[1] = (uint8_t)((b4[0].mode & 15) | (b4[1].mode & 15) << 4);
         lf->pad_[0] = (uint8_t)((b4[2].mode & 15) | (b4[3].mode & 15) << 4);
     }
+}
+
+/* The mixed stand-in (NOT the reference's mode decision either): svt_md_default_unit's partition with an intra alternative per PU, from
+ * the ME records and the open-loop intra search records of the same SB.  PU p (0 the 64x64, 1..4 the 32x32, 5..20 the 16x16, 21..84 the
+ * 8x8 blocks) and the OIS groups (32x32 at 0, 16x16 at 4, 8x8 at 20) number their blocks in the same z-order, so the OIS record of PU
+ * p >= 1 is ois[p - 1]; the 64x64 PU has none (the intra pass takes no 64x64 block).
+ *      inter(p) = the best ME candidate's distortion (svt_md_cost)
+ *      intra(p) = ois[p - 1].sad + intra_penalty, in 64 bits; none when the record's sad is UINT32_MAX, and for p = 0
+ *      cost(p)  = min(inter(p), intra(p));   a leaf p is intra iff intra(p) < inter(p) (ties go to inter)
+ * Luma against luma: ME's distortion is a luma SAD, so uv_sad takes no part.  The merge is svt_md_default_unit's with svt_md_cost
+ * replaced by cost: the same lambda terms, fit rules and 64-bit sums; no unit of four 4x4 blocks is produced (records 84.. are not read).
+ * An inter leaf is written as svt_md_default_unit writes it.  An intra leaf: sb_type 3 / 6 / 9 with the transform of its size, is_inter =
+ * skip = 0, pad_[1] / pad_[2] = the record's mode / uv_mode; in the prediction grid bw8 = bh8 = its size, ref_list = {-1, -1}, vectors 0.
+ * With intra_penalty >= 1 << 24 (above every SAD of a 64x64 block) no leaf of real ME records is intra and both grids are
+ * svt_md_default_unit's.  Returns 1 when the unit was written intra.  res = the SB's 85 ME records, ois = its first 84 OIS records. */
+SVT_HD uint64_t svt_md_mixed_intra(const svt_ois_block *ois, int pu, uint32_t intra_penalty) {
+    if (pu < 1 || ois[pu - 1].sad == SVT_OIS_NONE) return ~(uint64_t)0;
+    return (uint64_t)ois[pu - 1].sad + intra_penalty;
+}
+SVT_HD uint64_t svt_md_mixed_cost(const svt_me_pu_result *res, const svt_ois_block *ois, int pu, uint32_t intra_penalty) {
+    const uint64_t inter = svt_md_cost(res, pu), intra = svt_md_mixed_intra(ois, pu, intra_penalty);
+    return intra < inter ? intra : inter;
+}
+
+SVT_HD int svt_md_mixed_unit(const svt_me_pu_result *res, const svt_ois_block *ois, int r, int c, int sb_row, int sb_col, int mi_rows, int mi_cols,
+                             uint32_t lambda, uint32_t intra_penalty, int filter_level, svt_mc_mode_info *mc, svt_lf_mode_info *lf) {
+    const int ur0 = sb_row * 8, uc0 = sb_col * 8;
+    const int q32 = (r >> 2) * 2 + (c >> 2), q16 = ((r >> 1) & 1) * 2 + ((c >> 1) & 1), q8 = (r & 1) * 2 + (c & 1);
+    const int fit64 = ur0 + 8 <= mi_rows && uc0 + 8 <= mi_cols;
+    const int fit32 = ur0 + (r & ~3) + 4 <= mi_rows && uc0 + (c & ~3) + 4 <= mi_cols;
+    const int fit16 = ur0 + (r & ~1) + 2 <= mi_rows && uc0 + (c & ~1) + 2 <= mi_cols;
+    uint64_t cost64_children = 0;
+    int      merged32_here = 0, all32_fit = 1;
+    for (int a = 0; a < 4; a++) {
+        const int ar = (a >> 1) * 4, ac = (a & 1) * 4;
+        const int fits = ur0 + ar + 4 <= mi_rows && uc0 + ac + 4 <= mi_cols;
+        uint64_t  s16 = 0;
+        for (int k = 0; k < 4; k++) s16 += svt_md_mixed_cost(res, ois, 5 + 4 * a + k, intra_penalty);
+        const uint64_t p32 = svt_md_mixed_cost(res, ois, 1 + a, intra_penalty);
+        const int      merge = fits && p32 <= s16 + 3ull * lambda;
+        cost64_children += merge ? p32 + lambda : s16 + 4ull * lambda;
+        all32_fit &= fits;
+        if (a == q32) merged32_here = merge;
+    }
+    const int merge64 = fit64 && all32_fit && svt_md_mixed_cost(res, ois, 0, intra_penalty) + lambda <= cost64_children;
+    int pu, sb_type, tx, w8;
+    if (merge64) { pu = 0; sb_type = 12; tx = 3; w8 = 8; }
+    else if (merged32_here && fit32) { pu = 1 + q32; sb_type = 9; tx = 3; w8 = 4; }
+    else if (fit16) { pu = 5 + 4 * q32 + q16; sb_type = 6; tx = 2; w8 = 2; }
+    else { pu = 21 + 16 * q32 + 4 * q16 + q8; sb_type = 3; tx = 1; w8 = 1; }
+    const svt_me_pu_result *p = &res[pu];
+    const int intra = svt_md_mixed_intra(ois, pu, intra_penalty) < (uint64_t)svt_md_cost(res, pu);
+    const int d = (int)p->distortion_direction[0].direction; /* 0 list 0, 1 list 1, 2 bi-prediction */
+    mc->bw8 = mc->bh8 = (uint8_t)w8;
+    mc->ref_list[0] = (int8_t)(intra ? -1 : d == 1 ? 1 : 0);
+    mc->ref_list[1] = (int8_t)(!intra && d == 2 ? 1 : -1);
+    mc->mv_row[0] = (int16_t)(intra ? 0 : 2 * (d == 1 ? p->y_mv_l1 : p->y_mv_l0));
+    mc->mv_col[0] = (int16_t)(intra ? 0 : 2 * (d == 1 ? p->x_mv_l1 : p->x_mv_l0));
+    mc->mv_row[1] = (int16_t)(!intra && d == 2 ? 2 * p->y_mv_l1 : 0);
+    mc->mv_col[1] = (int16_t)(!intra && d == 2 ? 2 * p->x_mv_l1 : 0);
+    lf->sb_type = (uint8_t)sb_type; lf->tx_size = (uint8_t)tx; lf->skip = 0; lf->is_inter = (uint8_t)!intra; lf->filter_level = (uint8_t)filter_level;
+    lf->pad_[0] = 0;
+    lf->pad_[1] = (uint8_t)(intra ? ois[pu - 1].mode : 0);
+    lf->pad_[2] = (uint8_t)(intra ? ois[pu - 1].uv_mode : 0);
+    return intra;
 }
 
 /* ------------------------------------------------------------------------------------------------------------------------ */

@@ -96,11 +96,13 @@ template <int N, bool CH> __device__ __forceinline__ void ois_task(ois_lds &L, i
     if (g == 0) L.best[ois_best_index<N, CH>(b)] = inside ? best : 0xFFFFFFFFu;
 }
 
-__global__ __launch_bounds__(OIS_THREADS) void svt_ois_kernel(const uint8_t *__restrict__ src_y, const uint8_t *__restrict__ src_u, const uint8_t *__restrict__ src_v,
-                                                              int y_stride, int uv_stride, int width, int height, int sb_cols, uint32_t *__restrict__ out) {
-    __shared__ ois_lds L;
+/* the search of SB `sb` of one picture by one workgroup.  WITH_4X4 = false leaves phase 1 out (the 256 luma 4x4 blocks, 16 of the 44 wave
+ * tasks): records 84 .. 339 are then written as "none" */
+template <bool WITH_4X4>
+__device__ __forceinline__ void ois_sb(ois_lds &L, const uint8_t *__restrict__ src_y, const uint8_t *__restrict__ src_u, const uint8_t *__restrict__ src_v,
+                                       int y_stride, int uv_stride, int width, int height, int sb_cols, int sb, uint32_t *__restrict__ out) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sb = (int)blockIdx.x, sx = (sb % sb_cols) * 64, sy = (sb / sb_cols) * 64;
+    const int sx = (sb % sb_cols) * 64, sy = (sb / sb_cols) * 64;
     /* stage the SB with its border: 127 above the picture (the corner too), 129 left of it (and the corner below the picture's top row),
        0 outside the picture on the right / bottom (only blocks that are not inside read it; their records are discarded) */
     for (int i = tid; i < 65 * 65; i += OIS_THREADS) {
@@ -126,13 +128,15 @@ __global__ __launch_bounds__(OIS_THREADS) void svt_ois_kernel(const uint8_t *__r
     __syncthreads();
     /* phase 1: the 256 luma 4x4 blocks (one per thread builds its samples; a block in the left half of its 8x8 unit reads the true
        above-right samples) */
-    {
-        const int b = tid, x4 = ois_deint(b);
-        ois_build_edge(L, 0, 4, 4 * x4, 4 * ois_deint(b >> 1), !(x4 & 1), L.edge + b * 16);
+    if (WITH_4X4) {
+        {
+            const int b = tid, x4 = ois_deint(b);
+            ois_build_edge(L, 0, 4, 4 * x4, 4 * ois_deint(b >> 1), !(x4 & 1), L.edge + b * 16);
+        }
+        __syncthreads();
+        for (int t = wave; t < 16; t += OIS_THREADS / 64) ois_task<4, false>(L, t, sx, sy, width, height, lane);
+        __syncthreads();
     }
-    __syncthreads();
-    for (int t = wave; t < 16; t += OIS_THREADS / 64) ois_task<4, false>(L, t, sx, sy, width, height, lane);
-    __syncthreads();
     /* phase 2: 4 + 16 + 64 luma blocks of 32x32 / 16x16 / 8x8 and 2 x (4 + 16 + 64) chroma blocks (252 threads, one block each) */
     if (tid < 252) {
         int plane = 0, n, b, off;
@@ -158,12 +162,36 @@ __global__ __launch_bounds__(OIS_THREADS) void svt_ois_kernel(const uint8_t *__r
     /* the SB's records: three dwords each (sad, uv_sad, mode | uv_mode << 8) */
     uint32_t *o = out + (size_t)sb * SVT_OIS_PER_SB * 3;
     for (int i = tid; i < SVT_OIS_PER_SB; i += OIS_THREADS) {
-        const uint32_t y = L.best[i];
+        const uint32_t y = WITH_4X4 || i < 84 ? L.best[i] : 0xFFFFFFFFu;
         const uint32_t c = i < 84 ? L.best[OIS_CBEST + (i < 4 ? i : i < 20 ? 4 + (i - 4) : 20 + (i - 20))] : 0xFFFFFFFFu;
         o[3 * i + 0] = y == 0xFFFFFFFFu ? y : y >> 4;
         o[3 * i + 1] = c == 0xFFFFFFFFu ? c : c >> 4;
         o[3 * i + 2] = (y == 0xFFFFFFFFu ? 0xFFu : (y & 15u)) | (c == 0xFFFFFFFFu ? 0xFFu : (c & 15u)) << 8;
     }
+}
+
+__global__ __launch_bounds__(OIS_THREADS) void svt_ois_kernel(const uint8_t *__restrict__ src_y, const uint8_t *__restrict__ src_u, const uint8_t *__restrict__ src_v,
+                                                              int y_stride, int uv_stride, int width, int height, int sb_cols, uint32_t *__restrict__ out) {
+    __shared__ ois_lds L;
+    ois_sb<true>(L, src_y, src_u, src_v, y_stride, uv_stride, width, height, sb_cols, (int)blockIdx.x, out);
+}
+
+/* several pictures of one geometry in one launch: workgroup (picture, SB), the picture's planes and records from the staged descriptor */
+constexpr int OIS_MAX_PICS = 32;
+struct ois_pic_dev {
+    const uint8_t *y, *u, *v;
+    uint32_t      *out;
+    int32_t        y_stride, uv_stride;
+};
+struct ois_batch_dev {
+    ois_pic_dev pic[OIS_MAX_PICS];
+    int32_t     n_sb, sb_cols, width, height;
+};
+template <bool WITH_4X4> __global__ __launch_bounds__(OIS_THREADS) void svt_ois_batch_kernel(const ois_batch_dev *__restrict__ B) {
+    __shared__ ois_lds L;
+    const int          pic = (int)blockIdx.x / B->n_sb, sb = (int)blockIdx.x % B->n_sb;
+    const ois_pic_dev &P = B->pic[pic];
+    ois_sb<WITH_4X4>(L, P.y, P.u, P.v, P.y_stride, P.uv_stride, B->width, B->height, B->sb_cols, sb, P.out);
 }
 
 /* stand-in intra decision: one wave per SB, one lane per 8x8 unit, the SB's records in LDS */
@@ -195,6 +223,35 @@ extern "C" int32_t svt_hip_intra_search_device(svt_hip_ctx *ctx, const svt_yuv_p
     hipLaunchKernelGGL(svt_ois_kernel, dim3(n_sb), dim3(OIS_THREADS), 0, ctx->stream, (const uint8_t *)src->y, (const uint8_t *)src->u, (const uint8_t *)src->v,
                        src->y_stride, src->uv_stride, width, height, sb_cols, (uint32_t *)d_out);
     HIP_TRY(hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+extern "C" int32_t svt_hip_intra_search_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_yuv_planes *srcs, int32_t width, int32_t height, int32_t with_4x4,
+                                                     svt_ois_block *const *d_out) {
+    if (!ctx || n_pics < 1 || !srcs || !d_out || width < 8 || height < 8 || (width & 7) || (height & 7) || (with_4x4 != 0 && with_4x4 != 1))
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "intra_search_batch: bad argument");
+    for (int i = 0; i < n_pics; i++) /* (every picture is looked at before anything is launched) */
+        if (!srcs[i].y || !srcs[i].u || !srcs[i].v || !d_out[i] || srcs[i].y_stride < width || srcs[i].uv_stride < (width >> 1) || ((uintptr_t)d_out[i] & 3))
+            return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "intra_search_batch: bad picture");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int sb_cols = (width + 63) >> 6, n_sb = sb_cols * ((height + 63) >> 6);
+    for (int first = 0; first < n_pics; first += OIS_MAX_PICS) {
+        const int n = n_pics - first < OIS_MAX_PICS ? n_pics - first : OIS_MAX_PICS;
+        void     *h = nullptr, *d = nullptr;
+        if (svt_ctx_stage(ctx, sizeof(ois_batch_dev), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "intra_search_batch: descriptor buffers");
+        ois_batch_dev *hb = (ois_batch_dev *)h;
+        memset(hb, 0, sizeof *hb);
+        hb->n_sb = n_sb; hb->sb_cols = sb_cols; hb->width = width; hb->height = height;
+        for (int i = 0; i < n; i++) {
+            const svt_yuv_planes &s = srcs[first + i];
+            hb->pic[i].y = s.y; hb->pic[i].u = s.u; hb->pic[i].v = s.v; hb->pic[i].out = (uint32_t *)d_out[first + i];
+            hb->pic[i].y_stride = s.y_stride; hb->pic[i].uv_stride = s.uv_stride;
+        }
+        HIP_TRY(svt_ctx_stage_send(ctx, sizeof(ois_batch_dev)));
+        if (with_4x4) hipLaunchKernelGGL(svt_ois_batch_kernel<true>, dim3(n * n_sb), dim3(OIS_THREADS), 0, ctx->stream, (const ois_batch_dev *)d);
+        else hipLaunchKernelGGL(svt_ois_batch_kernel<false>, dim3(n * n_sb), dim3(OIS_THREADS), 0, ctx->stream, (const ois_batch_dev *)d);
+        HIP_TRY(hipGetLastError());
+    }
     return SVT_HIP_OK;
 }
 

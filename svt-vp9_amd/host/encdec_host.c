@@ -64,6 +64,27 @@ int32_t svt_hip_md_default_picture(const svt_me_pu_result *results, int32_t pic_
     return SVT_HIP_OK;
 }
 
+int32_t svt_hip_md_mixed_picture(const svt_me_pu_result *results, const svt_ois_block *ois, int32_t pic_width, int32_t pic_height, uint32_t lambda,
+                                 uint32_t intra_penalty, int32_t filter_level, svt_mc_mode_info *mc_mi, svt_lf_mode_info *lf_mi, int32_t mi_stride,
+                                 int32_t *intra_units) {
+    if (!results || !ois || !mc_mi || !lf_mi || !intra_units || pic_width < 8 || pic_height < 8 || (pic_width & 7) || (pic_height & 7) || filter_level < 0 ||
+        filter_level > 63)
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    const int mi_rows = pic_height >> 3, mi_cols = pic_width >> 3, sb_cols = (pic_width + 63) >> 6, sb_rows = (pic_height + 63) >> 6;
+    if (mi_stride < mi_cols) return SVT_HIP_ERR_BAD_PARAMETER;
+    int32_t n = 0;
+    for (int sr = 0; sr < sb_rows; sr++)
+        for (int sc = 0; sc < sb_cols; sc++)
+            for (int u = 0; u < 64; u++) {
+                const int r = u >> 3, c = u & 7, ur = sr * 8 + r, uc = sc * 8 + c;
+                if (ur >= mi_rows || uc >= mi_cols) continue;
+                n += svt_md_mixed_unit(results + (size_t)(sr * sb_cols + sc) * 85, ois + (size_t)(sr * sb_cols + sc) * SVT_OIS_PER_SB, r, c, sr, sc, mi_rows,
+                                       mi_cols, lambda, intra_penalty, filter_level, &mc_mi[ur * mi_stride + uc], &lf_mi[ur * mi_stride + uc]);
+            }
+    *intra_units = n;
+    return SVT_HIP_OK;
+}
+
 /* The transform blocks of n_pics pictures of one geometry, grouped by transform size; inside a size in the order picture, SB
  * (raster), unit of the SB (raster), and per unit luma, Cb, Cr -- the order the device-side builder produces.  size_count[4] and
  * (optionally) pos[] as the driver keeps them.  Returns the number of blocks, or a negative error (capacity too small, malformed

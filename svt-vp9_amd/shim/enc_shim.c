@@ -22,6 +22,9 @@
  *                                ring holds SVT_HIP_RING_GROUPS mini-GOPs) is overwritten behind the marker of its last reader on the main
  *                                context (device-side waits, svt_hip_ctx_wait_marker); the reconstruction copies of get_recon run on
  *                                an OUTPUT context the same way (SVT_HIP_SINGLE_STREAM=1: everything on the main stream)
+ *   inter pictures, opt-in       SVT_HIP_INTER_DECISION=mixed: the stand-in of an inter picture no callback decided compares ME with the open-loop
+ *                                intra search of its source (svt_hip_intra_search_batch_device + svt_hip_md_mixed_batch_device) and may hold
+ *                                intra leaves; the feeder waits for the wave's intra-unit counts (decision_source 3)
  *   intra pictures               coded by the intra encode pass (svt_hip_encdec_intra_device: wavefront prediction + transform, then
  *                                deblocking and border); the decision callback is asked for them too, the stand-in is 16x16 / DC
  *                                (SVT_HIP_INTRA_DECISION=search: the open-loop intra search + the grid built from its records); on a KEY
@@ -171,6 +174,13 @@ typedef struct shim_dev {
     void            *d_src_slab, *d_pred_slab, *d_q_slab, *d_dq_slab;
     void            *d_ois;          /* SVT_HIP_INTRA_DECISION=search: the open-loop intra search records of the key frame being decided (n_sb *
                                         SVT_OIS_PER_SB; written and read on the context of the intra pass, in stream order) */
+    /* SVT_HIP_INTER_DECISION=mixed: the open-loop intra search records of the inter pictures being decided (one buffer per picture of the
+       largest wave of the configured mini-GOP; written and read on the wave's context in stream order, and the feeder has waited for the
+       wave's counts before the next wave uses them) and the waves' intra-unit counts on the device and in pinned host memory */
+    void            *d_ois_mixed[SHIM_WAVE_MAX];
+    int              n_ois_mixed;
+    void            *d_intra_units;
+    int32_t         *h_intra_units;
     svt_encdec_work *work;
     shim_recon      *free_recon;     /* pinned buffers ready for re-use */
     /* The device's feeder: a thread that enqueues the planned groups of this device (motion estimation, statistics, the waves behind
@@ -217,6 +227,8 @@ typedef struct shim_state {
     int         q_index, filter_level;
     uint32_t    md_lambda;
     int         intra_search;          /* SVT_HIP_INTRA_DECISION=search: intra pictures no callback decided go through the open-loop intra search */
+    int         inter_mixed;           /* SVT_HIP_INTER_DECISION=mixed: inter pictures no callback decided get the mixed stand-in (intra leaves where the
+                                          open-loop intra search beats ME) */
     svt_lf_thresh thr;
     svt_vp9_shim_md_callback md_cb;
     void       *md_user;
@@ -392,6 +404,12 @@ static void free_dev(shim_state *s, shim_dev *d) {
     void *v[5] = {d->d_src_slab, d->d_pred_slab, d->d_q_slab, d->d_dq_slab, d->d_ois};
     for (int k = 0; k < 5; k++) svt_hip_mem_free(d->ctx, v[k]);
     d->d_src_slab = d->d_pred_slab = d->d_q_slab = d->d_dq_slab = d->d_ois = NULL;
+    for (int k = 0; k < SHIM_WAVE_MAX; k++) { svt_hip_mem_free(d->ctx, d->d_ois_mixed[k]); d->d_ois_mixed[k] = NULL; }
+    svt_hip_mem_free(d->ctx, d->d_intra_units);
+    d->d_intra_units = NULL;
+    if (d->h_intra_units) svt_hip_host_free(d->ctx, d->h_intra_units);
+    d->h_intra_units = NULL;
+    d->n_ois_mixed = 0;
     while (d->free_recon) { shim_recon *r = d->free_recon; d->free_recon = r->next; svt_hip_host_free(d->ctx, r->host); svt_hip_mem_free(d->ctx, r->d_tight); free(r); }
     if (d->work_key && d->work_key != d->work) svt_hip_encdec_work_destroy(d->ctx_key, d->work_key);
     d->work_key = NULL;
@@ -439,6 +457,15 @@ static int alloc_dev(shim_state *s, shim_dev *d) {
     if (ok && d->ctx_key != d->ctx) ok = svt_hip_encdec_work_create(d->ctx_key, 1, W, H, &d->work_key) == SVT_HIP_OK;
     else d->work_key = d->work;
     if (ok && s->intra_search) ok = svt_hip_mem_alloc(d->ctx, (size_t)s->n_sb * SVT_OIS_PER_SB * sizeof(svt_ois_block), &d->d_ois) == SVT_HIP_OK;
+    if (ok && s->inter_mixed) { /* the largest wave of a mini-GOP is its deepest layer: half its pictures */
+        d->n_ois_mixed = s->minigop / 2 < 1 ? 1 : s->minigop / 2 > SHIM_WAVE_MAX ? SHIM_WAVE_MAX : s->minigop / 2;
+        for (int k = 0; ok && k < d->n_ois_mixed; k++)
+            ok = svt_hip_mem_alloc(d->ctx, (size_t)s->n_sb * SVT_OIS_PER_SB * sizeof(svt_ois_block), &d->d_ois_mixed[k]) == SVT_HIP_OK;
+        void *hp = NULL;
+        ok = ok && svt_hip_mem_alloc(d->ctx, SHIM_WAVE_MAX * sizeof(int32_t), &d->d_intra_units) == SVT_HIP_OK &&
+             svt_hip_host_alloc(d->ctx, SHIM_WAVE_MAX * sizeof(int32_t), &hp) == SVT_HIP_OK;
+        d->h_intra_units = (int32_t *)hp;
+    }
     for (int i = 0; ok && i < d->n_slots; i++) {
         shim_slot *t = &d->slot[i];
         t->number = -1;
@@ -518,6 +545,15 @@ EbErrorType eb_vp9_init_encoder(EbComponentType *h) {
         else if (!strcmp(idm, "search")) s->intra_search = 1;
         else {
             fprintf(stderr, "SvtVp9Enc: SVT_HIP_INTRA_DECISION=%s: expected \"dc\" or \"search\"\n", idm);
+            return EB_ErrorBadParameter;
+        }
+    }
+    {   /* how inter pictures that no callback decides are decided; read per encoder like the intra rule above */
+        const char *edm = getenv("SVT_HIP_INTER_DECISION");
+        if (!edm || !*edm || !strcmp(edm, "default")) s->inter_mixed = 0;
+        else if (!strcmp(edm, "mixed")) s->inter_mixed = 1;
+        else {
+            fprintf(stderr, "SvtVp9Enc: SVT_HIP_INTER_DECISION=%s: expected \"default\" or \"mixed\"\n", edm);
             return EB_ErrorBadParameter;
         }
     }
@@ -858,6 +894,7 @@ static EbErrorType encode_wave(shim_state *s, shim_dev *d, const shim_job *const
     const uint32_t lambda_l = 4u * (uint32_t)svt_hip_vp9_ac_step(q_l);
     int n_stand_in = 0;
     int has_intra[SHIM_WAVE_MAX] = {0};
+    int stand_in_pic[SHIM_WAVE_MAX]; /* picture of the wave behind the k-th stand-in decision */
     const svt_me_pu_result *res[SHIM_WAVE_MAX];
     svt_mc_mode_info       *mcs[SHIM_WAVE_MAX];
     svt_lf_mode_info       *lfs[SHIM_WAVE_MAX];
@@ -885,7 +922,11 @@ static EbErrorType encode_wave(shim_state *s, shim_dev *d, const shim_job *const
                 for (size_t u = 0; u < (size_t)s->mi_rows * s->mi_cols && !has_intra[i]; u++) has_intra[i] = !g[u].is_inter;
             }
         }
-        if (!decided) { res[n_stand_in] = (const svt_me_pu_result *)t->d_results; mcs[n_stand_in] = (svt_mc_mode_info *)t->d_mc_mi; lfs[n_stand_in] = (svt_lf_mode_info *)t->d_lf_mi; n_stand_in++; }
+        if (!decided) {
+            res[n_stand_in] = (const svt_me_pu_result *)t->d_results; mcs[n_stand_in] = (svt_mc_mode_info *)t->d_mc_mi; lfs[n_stand_in] = (svt_lf_mode_info *)t->d_lf_mi;
+            stand_in_pic[n_stand_in++] = i;
+            if (s->inter_mixed) t->info.decision_source = 3;
+        }
         svt_encdec_picture *p = &pics[i];
         memset(p, 0, sizeof *p);
         p->d_mc_mi = (const svt_mc_mode_info *)t->d_mc_mi; p->d_lf_mi = (svt_lf_mode_info *)t->d_lf_mi;
@@ -897,6 +938,35 @@ static EbErrorType encode_wave(shim_state *s, shim_dev *d, const shim_job *const
         t->info.is_used_as_reference = wj[i]->used_as_ref; t->info.do_recon = fl.do_recon; t->info.apply_loop_filter = fl.apply_loop_filter;
         t->info.pad_reference = fl.pad_reference; t->info.q_index = q_l; t->info.filter_level = level_l; t->info.intra_recon_is_source = 0;
     }
+    if (n_stand_in && s->inter_mixed) {
+        /* the mixed stand-in: the open-loop intra search of the pictures' device-resident sources (no 4x4 phase: the rule makes no 4x4 unit),
+           then the decision, in sub-batches of the search buffers; the counts of intra units cross to pinned memory and the feeder waits
+           for them here -- has_intra selects the intra wavefront kernel behind the batch's transform stage.  intra_penalty = 2 lambda is an
+           untuned stand-in value (an intra leaf pays for its modes instead of its vectors), like the rule itself */
+        for (int b = 0; b < n_stand_in; b += d->n_ois_mixed) {
+            const int            m = n_stand_in - b < d->n_ois_mixed ? n_stand_in - b : d->n_ois_mixed;
+            svt_yuv_planes       srcs[SHIM_WAVE_MAX];
+            svt_ois_block       *outs[SHIM_WAVE_MAX];
+            svt_md_mixed_picture mp[SHIM_WAVE_MAX];
+            for (int k = 0; k < m; k++) {
+                srcs[k] = pics[stand_in_pic[b + k]].src;
+                outs[k] = (svt_ois_block *)d->d_ois_mixed[k];
+                mp[k].d_results = res[b + k]; mp[k].d_ois = outs[k]; mp[k].d_mc_mi = mcs[b + k]; mp[k].d_lf_mi = lfs[b + k];
+            }
+            GPU_TRY(svt_hip_intra_search_batch_device(cx, m, srcs, s->W, s->H, 0, outs));
+            GPU_TRY(svt_hip_md_mixed_batch_device(cx, m, mp, s->W, s->H, lambda_l, 2u * lambda_l, level_l, s->mi_cols, (int32_t *)d->d_intra_units));
+            uint64_t mk = 0;
+            GPU_TRY(svt_hip_mem_download_2d_async(cx, d->h_intra_units, (size_t)m * sizeof(int32_t), d->d_intra_units, (size_t)m * sizeof(int32_t),
+                                                  (size_t)m * sizeof(int32_t), 1));
+            GPU_TRY(svt_hip_ctx_marker_record(cx, &mk));
+            GPU_TRY(svt_hip_ctx_marker_wait(cx, mk));
+            for (int k = 0; k < m; k++) {
+                const int i = stand_in_pic[b + k];
+                has_intra[i] = d->h_intra_units[k] > 0;
+                pics[i].has_intra = has_intra[i];
+            }
+        }
+    }
     {   /* intra blocks need their neighbours' reconstruction: a wave that would not be reconstructed (the deepest layer without
            reconstructed output) is, when a host decision put intra blocks into it -- the reference reconstructs the SBs that hold them
            (is_intra_sb, Codec/EbEncDecProcess.c:3653-3657); the other flags of the wave stay */
@@ -907,7 +977,7 @@ static EbErrorType encode_wave(shim_state *s, shim_dev *d, const shim_job *const
             for (int i = 0; i < n; i++) ts[i]->info.do_recon = 1;
         }
     }
-    if (n_stand_in)
+    if (n_stand_in && !s->inter_mixed)
         GPU_TRY(svt_hip_md_default_batch_device(cx, n_stand_in, res, s->W, s->H, lambda_l, level_l, mcs, lfs, s->mi_cols));
     GPU_TRY(svt_hip_encdec_batch_device(cx, wk, n, pics, s->W, s->H, s->mi_cols, q_l, &fl, &s->thr, SHIM_REF_PAD, SHIM_REF_PAD));
     for (int i = 0; i < n; i++) {
