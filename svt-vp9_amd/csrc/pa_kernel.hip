@@ -25,13 +25,16 @@ struct pa_job {
 
 constexpr int PA_ROWS = 4; /* destination rows per workgroup */
 
-typedef uint32_t pa_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t pa_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+/* neither d_luma, luma_stride nor the plane strides are aligned to anything (a sixteenth plane of an 8x8 picture has rows 34 bytes
+ * apart): the vector types say so, as those of pa_stats.hip do.  Global loads and stores need no alignment on gfx950. */
+typedef uint32_t pa_u32x4 __attribute__((ext_vector_type(4), aligned(1)));
+typedef uint32_t pa_u32x2 __attribute__((ext_vector_type(2), aligned(1)));
+typedef uint32_t pa_u32 __attribute__((aligned(1)));
 
 /* 4 destination bytes whose sources lie inside the picture: `s` = address of the first source byte, consecutive destination
- * bytes are `step` source bytes apart.  Global loads need no alignment on gfx950: one load per destination dword. */
+ * bytes are `step` source bytes apart: one load per destination dword. */
 __device__ __forceinline__ uint32_t pa_dword_inside(const uint8_t PA_GLOBAL *s, int step) {
-    if (step == 1) return *(const uint32_t PA_GLOBAL *)s;
+    if (step == 1) return *(const pa_u32 PA_GLOBAL *)s;
     if (step == 2) {
         const pa_u32x2 d = *(const pa_u32x2 PA_GLOBAL *)s;
         return __builtin_amdgcn_perm(d.y, d.x, 0x06040200u);

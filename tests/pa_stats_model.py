@@ -208,3 +208,82 @@ SIGMAS = (0, 5, 8, 12, 25)  # flat level, flagged class 1, class 2, class 3, cla
 
 def noise_picture(w, h, sigma):
     return gen_picture(w, h, 100 + sigma, sigma)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# edge pictures: content at the ceilings of the arithmetic, and planes whose padding is not a copy of their edge
+# ------------------------------------------------------------------------------------------------------------------------------
+LUMA_KINDS = ("white", "black", "checker", "speck", "stripes_even", "stripes_odd", "halves", "random")
+CHROMA_KINDS = ("saturated", "zero", "random")
+
+
+def edge_luma(kind, w, h, seed=0):
+    """white: 255; black: 0; checker: ((x + y) & 1) * 255 (every interior noise sample is 128 or 0); speck: 255 where x and y are both
+    even; stripes_even / stripes_odd: 255 on even / odd rows (the 64x64 variance samples rows 0, 2, 4, 6 of a block only, so the two
+    differ); halves: 0 | 255 split inside every 8x8 block (the largest 8x8 variance); random: uniform 0..255."""
+    y, x = np.mgrid[0:h, 0:w]
+    if kind == "white":
+        p = np.full((h, w), 255)
+    elif kind == "black":
+        p = np.zeros((h, w))
+    elif kind == "checker":
+        p = ((x + y) & 1) * 255
+    elif kind == "speck":
+        p = ((x & 1) == 0) * ((y & 1) == 0) * 255
+    elif kind == "stripes_even":
+        p = ((y & 1) == 0) * 255
+    elif kind == "stripes_odd":
+        p = (y & 1) * 255
+    elif kind == "halves":
+        p = ((x >> 2) & 1) * 255
+    elif kind == "random":
+        p = np.random.default_rng(7000 + seed).integers(0, 256, (h, w))
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(p, dtype=np.uint8)
+
+
+def edge_chroma(kind, w, h, seed=0):
+    if kind == "saturated":
+        return np.full((h, w), 255, np.uint8)
+    if kind == "zero":
+        return np.zeros((h, w), np.uint8)
+    if kind == "random":
+        return np.random.default_rng(8000 + seed).integers(0, 256, (h, w), dtype=np.uint8)
+    raise ValueError(kind)
+
+
+def hostile_plane(pic, ox, oy, stride, seed):
+    """`pic` at (oy, ox) of a (h + 2 * oy) x stride buffer whose every other byte is seeded noise: a read that ought to be clamped to
+    the picture, or one with the wrong stride, does not return what the right read returns."""
+    h, w = pic.shape
+    assert stride >= w + ox
+    buf = np.random.default_rng(9000 + seed).integers(0, 256, (h + 2 * oy, stride), dtype=np.uint8)
+    buf[oy:oy + h, ox:ox + w] = pic
+    return buf
+
+
+# the ceiling pictures of noise detection: (method, analysed width, height, full width, height), each with both noise_detection_th and a
+# luma_height on each side of 720 and of 1080 (the class ladders' offsets)
+EDGE_NOISE_GEOMETRIES = ((FULL, 200, 196, 200, 196), (HALF, 136, 72, 544, 288), (QUARTER, 136, 72, 272, 144))
+EDGE_LUMA_HEIGHTS = (720, 1080, 1088)
+# (W, H, regions per width, per height): the reference's arrays end at 4 x 4 regions, the larger counts are the model's alone
+EDGE_HIST_CASES = ((200, 136, 3, 2), (72, 40, 3, 2), (328, 200, 3, 2), (200, 136, 4, 4), (72, 40, 4, 4), (328, 200, 4, 4), (200, 136, 1, 1))
+EDGE_HIST_MODEL_ONLY = ((200, 136, 8, 8), (328, 200, 5, 3))
+# 1, 3, 6 and 24 SBs: 1, 3, 2 and 15 of them complete; the first three leave a last workgroup of four SBs partly filled
+EDGE_SB_SIZES = ((64, 64), (192, 64), (136, 72), (328, 200))
+EDGE_MEANVAR_KINDS = ("white", "halves", "checker", "random")
+
+
+def edge_hist_planes(w, h, kind, seed):
+    """-> (luma, padded full luma buffer, its (ox, oy), cb, cr): a random luma in a hostile buffer of odd stride, chroma of `kind`"""
+    luma = edge_luma("random", w, h, seed)
+    ox, oy = 20, 7
+    return luma, hostile_plane(luma, ox, oy, w + 2 * ox + 5, seed), (ox, oy), edge_chroma(kind, w // 2, h // 2, seed + 1), edge_chroma(kind, w // 2, h // 2, seed + 2)
+
+
+def edge_meanvar_plane(kind, w, h, seed):
+    """-> (padded full luma buffer, origin_x, origin_y) of a block mean / variance case: the padding covers the partial SBs, which the
+    reference reads, and it is noise, so every reader has to agree on the stride as well"""
+    ox, oy = 68 + 3, 68
+    return hostile_plane(edge_luma(kind, w, h, seed), ox, oy, w + 2 * ox + 5, 60 + seed), ox, oy

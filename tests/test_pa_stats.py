@@ -101,6 +101,44 @@ def test_model_block_means_vs_reference_leaf_functions():
         assert int(q) == ref.eb_vp9_compute_subd_mean_of_squared_values8x8_sse2_intrin(p, C.c_uint16(s))
 
 
+@needs_ref
+@pytest.mark.parametrize("kind", M.LUMA_KINDS)
+def test_model_filter_vs_reference_leaf_functions_at_the_ceilings(kind):
+    """the ceiling pictures through both forms of the reference's filter, at widths with a partial last column"""
+    top = 0
+    for w, h in ((200, 196), (136, 72), (130, 70)):
+        pic = M.edge_luma(kind, w, h, 3)
+        den, noise = M.weak_filter(pic)
+        rden, rnoise = ref_weak_filter(pic)
+        assert np.array_equal(den, rden) and np.array_equal(noise, rnoise), (w, h)
+        top = max(top, int(noise.max()))
+    # a lone 255 among zeros: 255 - ((4 * 255) >> 3) = 128, the largest noise sample there is
+    assert top == {"white": 0, "black": 0, "checker": 128, "speck": 128, "stripes_even": 64, "stripes_odd": 64, "halves": 32}.get(kind, top)
+
+
+@needs_ref
+def test_model_block_means_vs_reference_leaf_functions_at_the_ceilings():
+    """8x8 blocks of the ceiling pictures, the all-255 block (mean of squares << 16 = 4 261 478 400) among them"""
+    ref = C.CDLL(REF_PA, mode=1)
+    fs = ("compute_mean", "compute_mean_of_squared_values", "eb_vp9_compute_sub_mean8x8_sse2_intrin",
+          "eb_vp9_compute_subd_mean_of_squared_values8x8_sse2_intrin", "eb_vp9_compute_mean8x8_avx2_intrin",
+          "eb_vp9_compute_mean_of_squared_values8x8_sse2_intrin")
+    for f in fs:
+        getattr(ref, f).restype = C.c_uint64
+    for kind in M.LUMA_KINDS:
+        a = M.edge_luma(kind, 40, 9, 5)
+        for off in (0, 3):  # aligned and not
+            p, s, blk = C.c_void_p(a.ctypes.data + a.strides[0] + off), a.strides[0], a[1:9, off:off + 8]
+            (m,), (q,) = (x.ravel() for x in M._sums8x8(blk, False))
+            assert int(m) == ref.compute_mean(p, s, 8, 8) == ref.eb_vp9_compute_mean8x8_avx2_intrin(p, s, 8, 8), kind
+            assert int(q) == ref.compute_mean_of_squared_values(p, s, 8, 8) == ref.eb_vp9_compute_mean_of_squared_values8x8_sse2_intrin(p, s, 8, 8), kind
+            (m,), (q,) = (x.ravel() for x in M._sums8x8(blk, True))
+            assert int(m) == ref.eb_vp9_compute_sub_mean8x8_sse2_intrin(p, C.c_uint16(s)), kind
+            assert int(q) == ref.eb_vp9_compute_subd_mean_of_squared_values8x8_sse2_intrin(p, C.c_uint16(s)), kind
+            if kind == "white":
+                assert int(q) == 4261478400 and int(m) == 255 << 8
+
+
 def test_model_vs_recorded_reference_outputs():
     """The fixture holds what the reference produced for pictures this test regenerates (M.noise_picture / M.gen_chroma; their CRCs are
     stored beside the outputs): the planes of its weak filter, and the outputs of detect_input_picture_noise, sub_sample_detect_noise,
