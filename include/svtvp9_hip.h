@@ -1667,6 +1667,133 @@ int32_t svt_ivf_stream_header(uint8_t out[SVT_IVF_STREAM_HEADER_BYTES], uint32_t
  * one-byte show-existing-frame headers with pts - 2, - 1, + 0, + 1).  Returns bytes written or a negative error. */
 int64_t svt_ivf_packetize(const uint8_t *packet, uint32_t len, uint64_t pts, int32_t show_ext, uint8_t *out, size_t capacity);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Entropy pass: what the encode pass leaves on the device -> VP9 packets, one entry for a batch of pictures.
+ *
+ * The counterpart of svt_hip_encdec_batch_device for everything behind it (csrc/entropy.hip): headers (host, into the packet
+ * descriptors) -> tokeniser -> inter mode labelling (inter pictures) -> mode info (svt_hip_modes_kf_batch_device over the intra-only
+ * pictures, svt_hip_modes_inter_batch_device over the others) -> gate -> bool coder -> result -> frame assembly, all on the context's
+ * stream, no host round trip, in that fixed order.  The stages are the existing entries; a workspace owns every buffer between them, sized
+ * by the caller's budgets, and a small kernel in front of the bool coder (the gate, rules in csrc/entropy_core.h) keeps a picture that
+ * exceeds a budget from being read past its buffers: its segment list is emptied, it gets no packet, and the result record says why.
+ * The probability tables are the caller's: svt_hip_boolcode_set_tables, svt_hip_modes_set_tables (when a batch holds an intra-only
+ * picture) and svt_hip_modes_inter_set_tables (when it holds any other) must have been called on the context.  The pass writes what it is
+ * told: svt_hip_entropy_deliverable says whether a decoder will read it. */
+typedef struct svt_entropy_limits {
+    uint32_t max_pics;       /* pictures a call may hold, 1 .. 32 */
+    uint32_t max_tokens;     /* PER PICTURE: token records */
+    uint32_t max_bools;      /* bools of the tile's stream, the mode-info stage's and the tokens' together (svt_bool_stream.max_bools: the
+                                context's bool-coder scratch grows with it) */
+    uint32_t max_tile_bytes; /* bytes of the coded tile */
+} svt_entropy_limits;
+/* limits no picture of the geometry exceeds: svt_hip_tokenize_capacity; svt_hip_boolcode_bools_capacity of it plus
+ * svt_hip_modes_inter_bools_capacity; svt_hip_boolcode_capacity of that.  All 0 for a geometry the stages do not take */
+void svt_hip_entropy_limits_worst(int32_t width, int32_t height, int32_t max_pics, svt_entropy_limits *out);
+/* device bytes svt_hip_entropy_work_create takes under these limits (0: it would refuse them).  Per picture, each part rounded up to 16:
+ * 4 * (W/4 * H/4 * 3/2) tok_off + 4 * (SBs + 1) sb_off + 4 * max_tokens + 12 * (H/8 * mi_stride) extension records
+ * + 2 * svt_hip_modes_inter_bools_capacity + 12 * svt_hip_modes_segments + max_tile_bytes + 64; times max_pics.
+ * The bool coder's scratch (about 11 bytes per bool of max_bools and picture) is the context's and is not counted here */
+uint64_t svt_hip_entropy_work_bytes(int32_t width, int32_t height, int32_t mi_stride, const svt_entropy_limits *limits);
+typedef struct svt_entropy_work svt_entropy_work; /* opaque */
+/* Refused: a null pointer, a geometry svt_hip_tokenize_batch_device refuses, max_pics outside 1 .. 32, max_bools beyond the bool coder's
+ * 32-bit bit positions (7 * (max_bools + 33) >= 2^32).  One workspace serves calls of that geometry on that context, one at a time:
+ * a call may be enqueued behind another (the stream orders them), the packets of the first are in the caller's arena by then */
+int32_t svt_hip_entropy_work_create(svt_hip_ctx *ctx, int32_t width, int32_t height, int32_t mi_stride, const svt_entropy_limits *limits, svt_entropy_work **work);
+void    svt_hip_entropy_work_destroy(svt_hip_ctx *ctx, svt_entropy_work *work);
+
+/* one picture of a batch; every pointer is a device pointer (host pointers in the host form); the grids have the workspace's mi_stride.
+ *   d_lf_mi, d_qcoeff, d_eob_map   what svt_hip_encdec_batch_device / svt_hip_encdec_intra_device leave (svt_tok_picture's inputs)
+ *   d_mc_mi     the prediction grid; NULL exactly when the picture is a key frame or intra_only
+ *   d_counts    the tokeniser's coef_counts (SVT_TOK_COUNTS, overwritten); may be NULL
+ *   frame       the two headers are written from it by svt_hip_frame_header_host; width and height are the workspace's; reference_mode,
+ *               allow_hp and ref_frame_sign_bias are also the mode stages' parameters
+ *   list_ref_frame, restrict_ref_mvs   as in svt_md_inter_picture (inter pictures)
+ *   trailer     up to four show-existing bytes behind the tile */
+typedef struct svt_entropy_picture {
+    const svt_lf_mode_info *d_lf_mi;
+    const svt_mc_mode_info *d_mc_mi;
+    const int16_t          *d_qcoeff;   /* 16-byte aligned */
+    const uint16_t         *d_eob_map;
+    uint32_t               *d_counts;
+    svt_frame_params        frame;
+    uint8_t                 list_ref_frame[2], restrict_ref_mvs, trailer_len, trailer[4];
+} svt_entropy_picture;                  /* 112 bytes */
+
+#define SVT_ENT_BAD_GRID 1u        /* a stage answered SVT_MODES_BAD_GRID */
+#define SVT_ENT_TOKENS_OVER 2u     /* the tokeniser's total > max_tokens */
+#define SVT_ENT_MODE_BOOLS_OVER 4u /* the mode-info stage's bools > its buffer (never under the stage's own capacity, which the workspace uses) */
+#define SVT_ENT_UNFAITHFUL_MV 8u   /* the labelling's d_status[2] != 0: a NEWMV leaf the syntax cannot code faithfully */
+#define SVT_ENT_STREAM_OVER 16u    /* the bool coder found more bools than max_bools */
+#define SVT_ENT_TILE_OVER 32u      /* the tile has more bytes than max_tile_bytes */
+/* flags 0: the picture has a packet.  tokens and mode_bools are the stages' totals as they wrote them (mode_bools SVT_MODES_BAD_GRID for a
+ * refused grid); tile_bytes is 0 for a picture without a packet; the leaf counts are the labelling's d_status[0 .. 2], 0 for an intra-only
+ * picture or a refused grid */
+typedef struct svt_entropy_result {
+    uint32_t flags, tokens, mode_bools, tile_bytes, inter_leaves, newmv_leaves, unfaithful_leaves, pad_;
+} svt_entropy_result;              /* 32 bytes */
+
+/* n_pics (<= the workspace's max_pics) pictures, key and inter pictures in any mix; packets, table and offsets as svt_hip_frame_batch_device
+ * documents them, in the caller's picture order: a picture whose flags are not 0 has size SVT_FRAME_SIZE_NONE, contributes no bytes and
+ * is counted in d_table[n_pics].size.  d_table (n_pics + 1 entries) and d_results (n_pics records, 4-byte aligned) may be device or pinned
+ * host memory, like d_arena.  Asynchronous on the context's stream, no synchronisation.
+ * Refused with SVT_HIP_ERR_BAD_PARAMETER, NOTHING launched: a null pointer (d_arena may be null when arena_capacity is 0); n_pics outside
+ * 1 .. max_pics; a workspace of another context; a null d_lf_mi / d_qcoeff / d_eob_map, d_qcoeff not 16-byte aligned; d_mc_mi null on an
+ * inter picture or set on a key / intra_only picture; trailer_len above 4; frame parameters svt_hip_frame_header_host refuses; frame.width /
+ * frame.height other than the workspace's; on an inter picture list_ref_frame outside 1 .. 3; tables (above) that have not been set */
+int32_t svt_hip_entropy_batch_device(svt_hip_ctx *ctx, svt_entropy_work *work, int32_t n_pics, const svt_entropy_picture *pics, uint8_t *d_arena,
+                                     uint32_t arena_capacity, svt_frame_entry *d_table, svt_entropy_result *d_results);
+/* profiling aid, like svt_hip_encdec_work_set_stage_hook: called on the enqueueing thread in front of every stage and once at the end */
+#define SVT_ENT_STAGE_HEADERS 0
+#define SVT_ENT_STAGE_TOKENS 1
+#define SVT_ENT_STAGE_LABELS 2
+#define SVT_ENT_STAGE_MODES 3
+#define SVT_ENT_STAGE_GATE 4
+#define SVT_ENT_STAGE_BOOLCODE 5
+#define SVT_ENT_STAGE_RESULT 6
+#define SVT_ENT_STAGE_FRAME 7
+#define SVT_ENT_STAGE_END 8
+void svt_hip_entropy_work_set_stage_hook(svt_entropy_work *work, void (*hook)(void *user, int32_t stage), void *user);
+/* where picture `pic` (0 .. max_pics - 1) of the workspace keeps its intermediates: for inspection and measurement */
+typedef struct svt_entropy_buffers {
+    uint32_t         *d_tok_off, *d_sb_off, *d_tokens;
+    svt_mi_inter_ext *d_ext;
+    uint32_t         *d_status;   /* the labelling's four words */
+    uint16_t         *d_bools;
+    svt_bool_segment *d_segments;
+    uint32_t         *d_n_bools;
+    uint8_t          *d_tile;
+    uint32_t         *d_tile_size, *d_verdict;
+    uint32_t          n_segments, n_sb;
+} svt_entropy_buffers;
+int32_t svt_hip_entropy_work_buffers(const svt_entropy_work *work, int32_t pic, svt_entropy_buffers *out);
+
+/* The same pass on host pointers, one picture (host/entropy_host.c): the stages' host forms in the same order and the same gate text; the
+ * model of the device entry.  packet (capacity bytes) receives header || tile || trailer; *packet_size its size, SVT_FRAME_SIZE_NONE for a
+ * picture without a packet (nothing is then written).  limits->max_pics is not read.  detail (may be NULL) reports what only the host
+ * knows.  Refused as the device entry refuses; also a packet_capacity below the packet's size */
+typedef struct svt_entropy_host_detail {
+    uint32_t stream_bools; /* bools of the tile's stream: what max_bools is compared with (0 when phase A withheld the picture) */
+    uint32_t header_bytes; /* the two headers together */
+    uint32_t coded_size;   /* the bool coder's answer: the tile's bytes (the empty stream's when phase A withheld the picture), or SVT_BOOL_SIZE_OVERFLOW */
+    uint32_t pad_;
+} svt_entropy_host_detail;
+int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
+                                const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
+                                uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail);
+/* the gate's two rules and the result record on plain values (csrc/entropy_core.h): status NULL for an intra-only picture.  Returns what
+ * the tile's size word becomes */
+uint32_t svt_hip_entropy_gate_host(uint32_t tok_total, uint32_t max_tokens, uint32_t n_bools, uint32_t bools_capacity, const uint32_t *status, uint32_t size,
+                                   uint32_t max_tile_bytes, uint32_t *verdict_a, svt_entropy_result *result);
+
+/* What a decoder needs beyond well-formed bytes (the findings of the frame reader); reported, not refused: the pass stays a faithful writer */
+#define SVT_ENT_NEEDS_BACKWARD_ADAPTATION 1u /* !error_resilient_mode && !frame_parallel_decoding_mode: a decoder adapts its probabilities */
+#define SVT_ENT_LOSSLESS 2u                  /* q index 0 and all delta qs 0: a decoder reads no tx_mode and runs the Walsh-Hadamard transform */
+#define SVT_ENT_COMP_FLAG_MISMATCH 4u        /* inter picture: allow_comp_inter_inter differs from "GOLDEN's or ALTREF's sign bias differs from LAST's" */
+#define SVT_ENT_REFERENCE_MODE_UNREAD 8u     /* inter picture: reference_mode is not SINGLE while that condition is false: a decoder assumes SINGLE */
+uint32_t svt_hip_entropy_deliverable(const svt_frame_params *p);
+/* comp_fixed_ref / comp_var_ref from cm->ref_frame_sign_bias: the rule of eb_vp9_setup_compound_reference_mode */
+void svt_hip_compound_refs_from_sign_bias(const uint8_t sign_bias[4], uint8_t *comp_fixed_ref, uint8_t comp_var_ref[2]);
+
 #ifdef __cplusplus
 }
 #endif

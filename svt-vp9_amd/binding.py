@@ -312,6 +312,9 @@ EXPORTS = [
     "svt_hip_md_inter_modes_batch_device", "svt_hip_md_inter_modes_picture",
     "svt_hip_frame_header_host", "svt_hip_frame_show_existing_host", "svt_hip_frame_batch_device", "svt_hip_frame_assemble_host", "svt_hip_frame_geometry",
     "svt_hip_recon_batch_device", "svt_hip_decode_batch_device", "svt_hip_decode_mixed_batch_device", "svt_hip_decode_intra_device", "svt_hip_frame_read_header_host", "svt_hip_tile_read_kf_host", "svt_hip_tile_read_host", "svt_hip_frame_read_host",
+    "svt_hip_entropy_limits_worst", "svt_hip_entropy_work_bytes", "svt_hip_entropy_work_create", "svt_hip_entropy_work_destroy", "svt_hip_entropy_batch_device",
+    "svt_hip_entropy_work_set_stage_hook", "svt_hip_entropy_work_buffers", "svt_hip_entropy_picture", "svt_hip_entropy_gate_host", "svt_hip_entropy_deliverable",
+    "svt_hip_compound_refs_from_sign_bias",
 ]
 
 _lib = None
@@ -379,6 +382,28 @@ def load():
         _lib.svt_hip_md_mixed_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _u32, _u32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         # (ctx, n_pics, srcs, width, height, with_4x4, d_out)
         _lib.svt_hip_intra_search_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        # entropy pass
+        _lib.svt_hip_entropy_limits_worst.restype = None
+        _lib.svt_hip_entropy_limits_worst.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        _lib.svt_hip_entropy_work_bytes.restype = C.c_uint64
+        _lib.svt_hip_entropy_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        _lib.svt_hip_entropy_work_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        _lib.svt_hip_entropy_work_destroy.restype = None
+        _lib.svt_hip_entropy_work_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        # (ctx, work, n_pics, pics, d_arena, arena_capacity, d_table, d_results)
+        _lib.svt_hip_entropy_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p, C.c_void_p]
+        _lib.svt_hip_entropy_work_set_stage_hook.restype = None
+        _lib.svt_hip_entropy_work_set_stage_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.svt_hip_entropy_work_buffers.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        # (bool tables, modes tables, inter tables, pic, mi_stride, limits, packet, packet_capacity, packet_size, result, detail)
+        _lib.svt_hip_entropy_picture.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.POINTER(_u32), C.c_void_p, C.c_void_p]
+        # (tok_total, max_tokens, n_bools, bools_capacity, status, size, max_tile_bytes, verdict_a, result)
+        _lib.svt_hip_entropy_gate_host.restype = _u32
+        _lib.svt_hip_entropy_gate_host.argtypes = [_u32, _u32, _u32, _u32, C.c_void_p, _u32, _u32, C.POINTER(_u32), C.c_void_p]
+        _lib.svt_hip_entropy_deliverable.restype = _u32
+        _lib.svt_hip_entropy_deliverable.argtypes = [C.c_void_p]
+        _lib.svt_hip_compound_refs_from_sign_bias.restype = None
+        _lib.svt_hip_compound_refs_from_sign_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -430,3 +455,30 @@ def plane_desc(arr, origin_x, origin_y, ptr=None):
     p.origin_x, p.origin_y = origin_x, origin_y
     p.width, p.height = w - 2 * origin_x, h - 2 * origin_y
     return p
+
+
+# entropy pass (svt_entropy_limits / svt_entropy_picture / svt_entropy_result / svt_entropy_buffers / svt_entropy_host_detail of include/svtvp9_hip.h)
+class EntropyLimits(C.Structure):
+    _fields_ = [("max_pics", C.c_uint32), ("max_tokens", C.c_uint32), ("max_bools", C.c_uint32), ("max_tile_bytes", C.c_uint32)]
+
+
+class EntropyPicture(C.Structure):
+    _fields_ = [("d_lf_mi", C.c_void_p), ("d_mc_mi", C.c_void_p), ("d_qcoeff", C.c_void_p), ("d_eob_map", C.c_void_p), ("d_counts", C.c_void_p),
+                ("frame", FrameParams), ("list_ref_frame", C.c_uint8 * 2), ("restrict_ref_mvs", C.c_uint8), ("trailer_len", C.c_uint8), ("trailer", C.c_uint8 * 4)]
+
+
+class EntropyBuffers(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("d_tok_off", "d_sb_off", "d_tokens", "d_ext", "d_status", "d_bools", "d_segments", "d_n_bools", "d_tile", "d_tile_size",
+                                          "d_verdict")] + [("n_segments", C.c_uint32), ("n_sb", C.c_uint32)]
+
+
+class EntropyHostDetail(C.Structure):
+    _fields_ = [("stream_bools", C.c_uint32), ("header_bytes", C.c_uint32), ("coded_size", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+ENTROPY_RESULT_DTYPE = np.dtype([(n, "<u4") for n in ("flags", "tokens", "mode_bools", "tile_bytes", "inter_leaves", "newmv_leaves", "unfaithful_leaves", "pad")])
+assert C.sizeof(EntropyPicture) == 112 and ENTROPY_RESULT_DTYPE.itemsize == 32 and C.sizeof(EntropyLimits) == 16
+ENT_BAD_GRID, ENT_TOKENS_OVER, ENT_MODE_BOOLS_OVER, ENT_UNFAITHFUL_MV, ENT_STREAM_OVER, ENT_TILE_OVER = 1, 2, 4, 8, 16, 32
+ENT_NEEDS_BACKWARD_ADAPTATION, ENT_LOSSLESS, ENT_COMP_FLAG_MISMATCH, ENT_REFERENCE_MODE_UNREAD = 1, 2, 4, 8
+ENT_STAGES = ("headers", "tokens", "labels", "modes", "gate", "boolcode", "result", "frame", "end")
+ENTROPY_STAGE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)

@@ -1,0 +1,221 @@
+/*
+ * entropy.hip -- the entropy pass over a batch of pictures (gfx950): one entry from what the encode pass leaves on the device to dense
+ * VP9 packets, the counterpart of svt_hip_encdec_batch_device behind it.
+ *
+ * The driver calls the existing stage entries in their fixed order on the context's stream -- tokeniser, inter mode labelling, the two
+ * mode-info stages, bool coder, frame assembly -- over buffers of a workspace sized by the caller's budgets, and puts two small kernels
+ * of its own round the bool coder (rules: csrc/entropy_core.h):
+ *   svt_ent_gate_kernel     ENT_WGS workgroups per picture (grid.y = picture).  Every lane reads the picture's seven words -- the
+ *                           tokeniser's total, the mode-info total, the labelling's four status words -- and derives the verdict
+ *                           itself: no LDS, no second launch.  For a verdict that is not 0 the workgroups zero the picture's segment
+ *                           list in a grid-stride loop of 16-byte stores (a record is {first, count, kind}: every count becomes 0), so
+ *                           the bool coder codes the empty stream and reads neither tokens nor bools.  Lane 0 of workgroup 0 keeps the
+ *                           verdict for the second phase.
+ *   svt_ent_result_kernel   one workgroup, lane i = picture i, behind the bool coder: STREAM_OVER / TILE_OVER from the tile's size, the
+ *                           caller's result record, and SVT_BOOL_SIZE_OVERFLOW over the size of every picture that does not ship, which
+ *                           is the frame stage's documented way to give a picture no packet.
+ * Bounds: the zeroing touches the n_sb * 192 vectors of the picture's own list inside the slab; the result kernel writes n_pics records
+ * and n_pics size words.  Plain vector stores, no atomics, no LDS.
+ */
+#include <hip/hip_runtime.h>
+#include <new>
+#include "svt_ctx.h"
+#include "entropy_core.h"
+
+#ifndef ENT_WGS
+#define ENT_WGS 8         /* workgroups per picture: with 256 lanes x 16 bytes, 32 KiB of the list a pass (a 2160p list is 6.2 MB) */
+#endif
+#define ENT_LANES 256
+
+extern "C" int32_t svt_entropy_check_limits(int32_t width, int32_t height, int32_t mi_stride, const svt_entropy_limits *limits, svt_ent_layout *l);
+extern "C" int32_t svt_entropy_check_picture(const svt_entropy_picture *p, int32_t width, int32_t height, uint8_t *header, uint32_t *header_len);
+
+struct svt_entropy_work {
+    svt_hip_ctx       *ctx;
+    int32_t            width, height, mi_stride;
+    svt_entropy_limits limits;
+    svt_ent_layout     l;
+    uint8_t           *slab;
+    void             (*hook)(void *user, int32_t stage);
+    void              *hook_user;
+};
+
+#define ENT_STAGE(k) do { if (w->hook) w->hook(w->hook_user, (k)); } while (0)
+
+namespace {
+
+struct ent_pic_dev {
+    const uint32_t     *tok_total, *n_bools, *status; /* status: null for an intra-only picture */
+    uint4              *segs;
+    uint32_t           *size, *verdict;
+    svt_entropy_result *result;
+    uint32_t            bools_capacity, pad_;
+};
+struct ent_batch_dev {
+    ent_pic_dev pic[SVT_FRAME_MAX_PICS];
+    uint32_t    max_tokens, max_tile_bytes, n_vec; /* n_vec: 16-byte vectors of a segment list */
+    int32_t     n_pics;
+};
+
+__global__ __launch_bounds__(ENT_LANES) void svt_ent_gate_kernel(const ent_batch_dev *__restrict__ B) {
+    const ent_pic_dev &P = B->pic[blockIdx.y];
+    const uint32_t     verdict = svt_ent_verdict_a(*P.tok_total, B->max_tokens, *P.n_bools, P.bools_capacity, svt_ent_status_of(P.status));
+    if (blockIdx.x == 0 && threadIdx.x == 0) *P.verdict = verdict;
+    if (!verdict) return;
+    const uint4    zero = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t n_vec = B->n_vec;
+    for (uint32_t v = blockIdx.x * ENT_LANES + threadIdx.x; v < n_vec; v += ENT_WGS * ENT_LANES) P.segs[v] = zero;
+}
+
+__global__ __launch_bounds__(64) void svt_ent_result_kernel(const ent_batch_dev *__restrict__ B) {
+    const int pic = (int)threadIdx.x;
+    if (pic >= B->n_pics) return;
+    const ent_pic_dev &P = B->pic[pic];
+    const uint32_t     size = *P.size, flags = svt_ent_verdict_b(*P.verdict, size, B->max_tile_bytes);
+    svt_entropy_result r;
+    const uint32_t     out = svt_ent_result_of(flags, *P.tok_total, *P.n_bools, size, svt_ent_status_of(P.status), &r);
+    uint32_t *const    d = (uint32_t *)P.result;
+    d[0] = r.flags; d[1] = r.tokens; d[2] = r.mode_bools; d[3] = r.tile_bytes;
+    d[4] = r.inter_leaves; d[5] = r.newmv_leaves; d[6] = r.unfaithful_leaves; d[7] = 0u;
+    if (flags) *P.size = out;
+}
+
+void buffers_of(const svt_entropy_work *w, int pic, svt_entropy_buffers *b) {
+    uint8_t *const  base = w->slab + (size_t)pic * (size_t)w->l.bytes;
+    uint32_t *const words = (uint32_t *)(base + w->l.words);
+    b->d_tok_off = (uint32_t *)(base + w->l.tok_off); b->d_sb_off = (uint32_t *)(base + w->l.sb_off); b->d_tokens = (uint32_t *)(base + w->l.tokens);
+    b->d_ext = (svt_mi_inter_ext *)(base + w->l.ext); b->d_status = words + SVT_ENT_W_STATUS; b->d_bools = (uint16_t *)(base + w->l.bools);
+    b->d_segments = (svt_bool_segment *)(base + w->l.segments); b->d_n_bools = words + SVT_ENT_W_N_BOOLS; b->d_tile = base + w->l.tile;
+    b->d_tile_size = words + SVT_ENT_W_SIZE; b->d_verdict = words + SVT_ENT_W_VERDICT;
+    b->n_segments = w->l.n_segments; b->n_sb = (uint32_t)w->l.n_sb;
+}
+
+} // namespace
+
+extern "C" int32_t svt_hip_entropy_work_create(svt_hip_ctx *ctx, int32_t width, int32_t height, int32_t mi_stride, const svt_entropy_limits *limits,
+                                               svt_entropy_work **work) {
+    svt_ent_layout l;
+    if (!ctx || !work || svt_entropy_check_limits(width, height, mi_stride, limits, &l)) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "entropy: bad workspace argument");
+    *work = nullptr;
+    HIP_TRY(hipSetDevice(ctx->device));
+    svt_entropy_work *w = new (std::nothrow) svt_entropy_work();
+    if (!w) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "entropy: workspace");
+    w->ctx = ctx; w->width = width; w->height = height; w->mi_stride = mi_stride; w->limits = *limits; w->l = l;
+    const size_t bytes = (size_t)l.bytes * limits->max_pics;
+    if (hipMalloc((void **)&w->slab, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        delete w;
+        return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "entropy: workspace slab");
+    }
+    *work = w;
+    return SVT_HIP_OK;
+}
+
+extern "C" void svt_hip_entropy_work_destroy(svt_hip_ctx *ctx, svt_entropy_work *w) {
+    if (!w) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream); /* (a call in flight may still use the slab) */
+    }
+    (void)hipFree(w->slab);
+    delete w;
+}
+
+extern "C" void svt_hip_entropy_work_set_stage_hook(svt_entropy_work *w, void (*hook)(void *user, int32_t stage), void *user) {
+    if (!w) return;
+    w->hook = hook;
+    w->hook_user = user;
+}
+
+extern "C" int32_t svt_hip_entropy_work_buffers(const svt_entropy_work *w, int32_t pic, svt_entropy_buffers *out) {
+    if (!w || !out || pic < 0 || (uint32_t)pic >= w->limits.max_pics) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "entropy: bad argument");
+    buffers_of(w, pic, out);
+    return SVT_HIP_OK;
+}
+
+extern "C" int32_t svt_hip_entropy_batch_device(svt_hip_ctx *ctx, svt_entropy_work *w, int32_t n_pics, const svt_entropy_picture *pics, uint8_t *d_arena,
+                                                uint32_t arena_capacity, svt_frame_entry *d_table, svt_entropy_result *d_results) {
+    if (!ctx || !w || w->ctx != ctx || !pics || !d_table || !d_results || ((uintptr_t)d_results & 3) || (!d_arena && arena_capacity) || n_pics < 1 ||
+        (uint32_t)n_pics > w->limits.max_pics)
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "entropy: bad argument");
+    /* everything a stage would refuse, in front of the first launch */
+    ENT_STAGE(SVT_ENT_STAGE_HEADERS);
+    svt_frame_packet        packets[SVT_FRAME_MAX_PICS];
+    svt_tok_picture         tok[SVT_FRAME_MAX_PICS];
+    svt_md_inter_picture    label[SVT_FRAME_MAX_PICS];
+    svt_modes_picture       key[SVT_FRAME_MAX_PICS];
+    svt_modes_inter_picture inter[SVT_FRAME_MAX_PICS];
+    svt_bool_stream         streams[SVT_FRAME_MAX_PICS];
+    ent_batch_dev           hb;
+    int                     n_key = 0, n_inter = 0;
+    memset(packets, 0, sizeof packets); memset(tok, 0, sizeof tok); memset(label, 0, sizeof label); memset(key, 0, sizeof key);
+    memset(inter, 0, sizeof inter); memset(streams, 0, sizeof streams); memset(&hb, 0, sizeof hb);
+    for (int i = 0; i < n_pics; i++) {
+        const svt_entropy_picture &p = pics[i];
+        uint32_t                   header_len = 0;
+        if (svt_entropy_check_picture(&p, w->width, w->height, packets[i].header, &header_len)) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "entropy: bad picture");
+        svt_entropy_buffers b;
+        buffers_of(w, i, &b);
+        const bool intra = svt_ent_intra_only(&p.frame) != 0;
+        tok[i].d_lf_mi = p.d_lf_mi; tok[i].d_qcoeff = p.d_qcoeff; tok[i].d_eob_map = p.d_eob_map; tok[i].d_tokens = b.d_tokens; tok[i].capacity = w->limits.max_tokens;
+        tok[i].d_tok_off = b.d_tok_off; tok[i].d_sb_off = b.d_sb_off; tok[i].d_counts = p.d_counts;
+        if (intra) {
+            svt_modes_picture &k = key[n_key++];
+            k.d_lf_mi = p.d_lf_mi; k.d_eob_map = p.d_eob_map; k.d_tok_off = b.d_tok_off; k.d_bools = b.d_bools; k.d_segments = b.d_segments; k.d_n_bools = b.d_n_bools;
+            k.capacity = w->l.kf_bools;
+        } else {
+            svt_md_inter_picture &d = label[n_inter];
+            d.d_lf_mi = p.d_lf_mi; d.d_mc_mi = p.d_mc_mi; d.d_ext_out = b.d_ext; d.d_status = b.d_status;
+            memcpy(d.list_ref_frame, p.list_ref_frame, 2);
+            memcpy(d.ref_frame_sign_bias, p.frame.ref_frame_sign_bias, 4);
+            d.restrict_ref_mvs = p.restrict_ref_mvs; d.allow_hp = p.frame.allow_hp; d.reference_mode = p.frame.reference_mode;
+            svt_ent_compound_refs(p.frame.ref_frame_sign_bias, &d.comp_fixed_ref, d.comp_var_ref);
+            svt_modes_inter_picture &m = inter[n_inter++];
+            m.d_lf_mi = p.d_lf_mi; m.d_eob_map = p.d_eob_map; m.d_tok_off = b.d_tok_off; m.d_bools = b.d_bools; m.d_segments = b.d_segments; m.d_n_bools = b.d_n_bools;
+            m.capacity = w->l.inter_bools; m.d_mc_mi = p.d_mc_mi; m.d_ext = b.d_ext;
+            m.reference_mode = d.reference_mode; m.allow_hp = d.allow_hp; m.comp_fixed_ref = d.comp_fixed_ref;
+            memcpy(m.comp_var_ref, d.comp_var_ref, 2);
+            memcpy(m.ref_frame_sign_bias, d.ref_frame_sign_bias, 4);
+        }
+        svt_bool_stream &s = streams[i];
+        s.d_tokens = b.d_tokens; s.d_bools = b.d_bools; s.d_segments = b.d_segments; s.d_n_tokens = b.d_sb_off + w->l.n_sb; s.n_segments = b.n_segments;
+        s.max_bools = w->limits.max_bools; s.capacity = w->limits.max_tile_bytes; s.d_bytes = b.d_tile; s.d_size = b.d_tile_size;
+        svt_frame_packet &q = packets[i];
+        q.d_tile = b.d_tile; q.d_tile_size = b.d_tile_size; q.tile_capacity = w->limits.max_tile_bytes; q.header_len = (uint8_t)header_len;
+        q.trailer_len = p.trailer_len;
+        memcpy(q.trailer, p.trailer, 4);
+        ent_pic_dev &P = hb.pic[i];
+        P.tok_total = b.d_sb_off + w->l.n_sb; P.n_bools = b.d_n_bools; P.status = intra ? nullptr : b.d_status; P.segs = (uint4 *)b.d_segments; P.size = b.d_tile_size;
+        P.verdict = b.d_verdict; P.result = d_results + i; P.bools_capacity = intra ? w->l.kf_bools : w->l.inter_bools;
+    }
+    hb.max_tokens = w->limits.max_tokens; hb.max_tile_bytes = w->limits.max_tile_bytes; hb.n_vec = w->l.n_segments / 4 * 3; hb.n_pics = n_pics;
+    if (!ctx->slot_bytes[SVT_SLOT_BC_TABLES] || (n_key && !ctx->slot_bytes[SVT_SLOT_MI_TABLES]) || (n_inter && !ctx->slot_bytes[SVT_SLOT_MII_TABLES]))
+        return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "entropy: the bool coder's or a mode-info stage's tables have not been set");
+    HIP_TRY(hipSetDevice(ctx->device));
+
+    int32_t rc;
+    ENT_STAGE(SVT_ENT_STAGE_TOKENS);
+    if ((rc = svt_hip_tokenize_batch_device(ctx, n_pics, tok, w->width, w->height, w->mi_stride))) return rc;
+    ENT_STAGE(SVT_ENT_STAGE_LABELS);
+    if (n_inter && (rc = svt_hip_md_inter_modes_batch_device(ctx, n_inter, label, w->width, w->height, w->mi_stride))) return rc;
+    ENT_STAGE(SVT_ENT_STAGE_MODES);
+    if (n_key && (rc = svt_hip_modes_kf_batch_device(ctx, n_key, key, w->width, w->height, w->mi_stride))) return rc;
+    if (n_inter && (rc = svt_hip_modes_inter_batch_device(ctx, n_inter, inter, w->width, w->height, w->mi_stride))) return rc;
+    ENT_STAGE(SVT_ENT_STAGE_GATE);
+    void *h = nullptr, *d = nullptr;
+    if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "entropy: descriptor buffers");
+    memcpy(h, &hb, sizeof hb);
+    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
+    const ent_batch_dev *dB = (const ent_batch_dev *)d; /* both phases read it: the slot is not taken again before 63 further uploads, each behind these kernels on the stream */
+    hipLaunchKernelGGL(svt_ent_gate_kernel, dim3(ENT_WGS, (unsigned)n_pics), dim3(ENT_LANES), 0, ctx->stream, dB);
+    HIP_TRY(hipGetLastError());
+    ENT_STAGE(SVT_ENT_STAGE_BOOLCODE);
+    if ((rc = svt_hip_boolcode_batch_device(ctx, n_pics, streams))) return rc;
+    ENT_STAGE(SVT_ENT_STAGE_RESULT);
+    hipLaunchKernelGGL(svt_ent_result_kernel, dim3(1), dim3(64), 0, ctx->stream, dB);
+    HIP_TRY(hipGetLastError());
+    ENT_STAGE(SVT_ENT_STAGE_FRAME);
+    if ((rc = svt_hip_frame_batch_device(ctx, n_pics, packets, d_arena, arena_capacity, d_table))) return rc;
+    ENT_STAGE(SVT_ENT_STAGE_END);
+    return SVT_HIP_OK;
+}
