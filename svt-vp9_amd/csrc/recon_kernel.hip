@@ -16,7 +16,8 @@
  * (row_load), the row <-> column change goes through the block's N x (N + 1) dword LDS tile, ordered with tq_block_sync -- the lanes of
  * a block sit in one wave, there is no workgroup barrier.  Workgroups are persistent and walk their XCD's eighth of the list (tq_walk_of).
  * The text of the inverse is tq_block_body's, statement for statement (that body is not edited to share it: tests/test_gpu_decode.py ties
- * the two by equality of the reconstruction bytes); it lives in rc_core.h (rc_block_body), which the intra decode kernel
+ * the two by equality of the reconstruction bytes, tests/test_gpu_recon_edges.py ties this copy to the reference's recorded bytes on
+ * coefficients the forward path never makes); it lives in rc_core.h (rc_block_body), which the intra decode kernel
  * (intra_recon_kernel.hip) shares.  No inline assembly; every store is a vector store.
  *
  * Two launch forms: descriptor lists (svt_hip_recon_batch_device: svt_hip_tq_batch_device's svt_tq_block lists, eob per list entry) and
