@@ -4,6 +4,7 @@ the last; Codec/EbEncHandle.c:2837-2865), and every byte equals the oracle chain
 each picture predicted from the RECONSTRUCTED, deblocked (where the reference deblocks), padded pictures before it.  Both decision
 sources: the built-in stand-in and a host callback (svt_vp9_shim_set_mode_decision)."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -154,9 +155,11 @@ def run_clip(W, H, N, enc_mode, tune, qp, recon_file, intra_period, use_callback
             packets.append((int(pp.contents.pts), int(pp.contents.flags)))
             lib.eb_vp9_svt_release_out_buffer(C.byref(pp))
     infos, refpics = {}, {}
+    planes = []                                                    # every input plane lives until deinit (SVT_HIP_REGISTER_INPUT=1 page-locks them)
     for n in range(N):
         y = np.ascontiguousarray(frames[n])
         u, v = (np.ascontiguousarray(p) for p in chroma(y, n))
+        planes.append((y, u, v))
         i = In(y.ctypes.data, u.ctypes.data, v.ctypes.data, None, None, None, W, W // 2, W // 2)
         b = Hdr(size=C.sizeof(Hdr), p_buffer=C.addressof(i), pts=n, flags=1 if n == N - 1 else 0)
         assert lib.eb_vp9_svt_enc_send_picture(h, C.byref(b)) == 0
@@ -186,6 +189,7 @@ def run_clip(W, H, N, enc_mode, tune, qp, recon_file, intra_period, use_callback
         assert lib.svt_vp9_shim_get_reference_picture(h, C.c_uint64(k), vp(out), C.c_uint64(out.size)) == 0
         refpics[k] = out
     assert lib.eb_vp9_deinit_encoder(h) == 0 and lib.eb_vp9_deinit_handle(h) == 0
+    del planes
     return frames, recon, order, flags_seen, packets, infos, refpics, seen
 
 
@@ -407,23 +411,37 @@ def test_without_recon_output_only_reference_pictures_are_reconstructed():
     assert kinds == {(1, 1, 1), (1, 0, 1), (0, 0, 0)}
 
 
+LONG_CLIP = (136, 72, 90, 8, 1, 40, 39)                        # W, H, N, enc_mode, tune, qp, intra_period
+
+
+@functools.lru_cache(maxsize=None)
+def long_clip_and_oracle():
+    """the long clip and its oracle chain: they depend on the clip alone, so every id below shares them (read only)"""
+    W, H, N, enc_mode, tune, qp, intra_period = LONG_CLIP
+    base = T.gen_clip_subpel(W, H, 30, 53)
+    clip = [base[i % 30] if (i // 30) % 2 == 0 else base[29 - i % 30] for i in range(N)]          # 30 pictures forth and back
+    recs, _ = oracle_clip(clip, W, H, N, enc_mode, tune, qp, 1, intra_period, False)
+    return clip, recs
+
+
 @pytest.mark.parametrize("env", [
     {"SVT_HIP_RING_GROUPS": "2"},                                                  # the smallest ring, feeder thread, upload / key streams (the defaults)
     {"SVT_HIP_RING_GROUPS": "2", "SVT_HIP_FEEDER": "0"},                           # everything enqueued by the caller's thread
     {"SVT_HIP_RING_GROUPS": "2", "SVT_HIP_DEEP_STREAM": "1"},                      # + the deep-layer stream
     {"SVT_HIP_RING_GROUPS": "3", "SVT_HIP_NO_KEY_STREAM": "1", "SVT_HIP_NO_UPLOAD_STREAM": "1"},
     {},                                                                            # the default ring of four mini-GOPs
-], ids=["ring2", "ring2-nofeeder", "ring2-deep", "ring3-nokey-noupload", "default"])
+    {"SVT_HIP_RING_GROUPS": "2", "SVT_HIP_SINGLE_STREAM": "1"},                    # everything on the main stream
+    {"SVT_HIP_RING_GROUPS": "2", "SVT_HIP_ME_STREAM": "1"},                        # + the ME stream (off by default with reconstructed output)
+    {"SVT_HIP_RING_GROUPS": "2", "SVT_HIP_DEVICES": "0,0", "SVT_HIP_SHARE_STREAMS": "0"},   # two contexts of one GPU, each with streams of its own
+], ids=["ring2", "ring2-nofeeder", "ring2-deep", "ring3-nokey-noupload", "default", "ring2-single", "ring2-me", "ring2-two-contexts-own-streams"])
 def test_long_clip_reuses_every_picture_slot_several_times(env):
     """90 pictures with an intra refresh every 40: every slot of a 34-picture ring is overwritten two or three times while the upload, input,
     main, key and output streams run side by side and the device's feeder thread enqueues the groups -- a slot must not be overwritten before
     its last reader (the marker chain of the library) nor read before its upload, whatever the set of streams and threads.  Every
     reconstruction still equals the oracle chain."""
-    W, H, N, enc_mode, tune, qp, intra_period = 136, 72, 90, 8, 1, 40, 39
-    base = T.gen_clip_subpel(W, H, 30, 53)
-    clip = [base[i % 30] if (i // 30) % 2 == 0 else base[29 - i % 30] for i in range(N)]          # 30 pictures forth and back
+    W, H, N, enc_mode, tune, qp, intra_period = LONG_CLIP
+    clip, recs = long_clip_and_oracle()
     frames, recon, order, flags_seen, packets, infos, refpics, _ = run_clip(W, H, N, enc_mode, tune, qp, 1, intra_period, False, frames=clip, env=env)
-    recs, outs = oracle_clip(frames, W, H, N, enc_mode, tune, qp, 1, intra_period, False)
     assert sorted(order) == list(range(N)) and len(packets) == N and packets[-1][1] & 1 and flags_seen[-1] == 1
     for k in range(N):
         y, u, v = recs[k].interior()
