@@ -1,6 +1,6 @@
 /*
  * recon_kernel.hip -- quantised coefficients -> dequantise -> inverse DCT / ADST -> add to the prediction -> clip, for batches of VP9
- * transform blocks (gfx950): the arithmetic of a decoder's reconstruction, and the second half of tq_block_body (tq_core.h) on its own.
+ * transform blocks (gfx950): the arithmetic of a decoder's reconstruction, run by the reconstruction half of the encode pass (tq_core.h).
  *
  * What a non-high-bit-depth decoder does per transform block (the VP9 specification's reconstruction process; the same arithmetic as the
  * tail of perform_coding_loop, Source/Lib/Codec/EbEncDecProcess.c:365-587: eb_vp9_quantize_b[_32x32]'s dqcoeff, VPX/quantize.c:112-254, then
@@ -15,10 +15,10 @@
  * coefficients (16-byte vector loads: coeff_off is a multiple of 8 coefficients and the array 16-byte aligned) and of the prediction
  * (row_load), the row <-> column change goes through the block's N x (N + 1) dword LDS tile, ordered with tq_block_sync -- the lanes of
  * a block sit in one wave, there is no workgroup barrier.  Workgroups are persistent and walk their XCD's eighth of the list (tq_walk_of).
- * The text of the inverse is tq_block_body's, statement for statement (that body is not edited to share it: tests/test_gpu_decode.py ties
- * the two by equality of the reconstruction bytes, tests/test_gpu_recon_edges.py ties this copy to the reference's recorded bytes on
- * coefficients the forward path never makes); it lives in rc_core.h (rc_block_body), which the intra decode kernel
- * (intra_recon_kernel.hip) shares.  No inline assembly; every store is a vector store.
+ * The inverse and the clip-add are the encode pass's own code: rc_block_body (rc_core.h, shared with the intra decode kernel,
+ * intra_recon_kernel.hip) dequantises and calls tq_recon_tail (tq_core.h), which tq_block_body calls behind its quantiser
+ * (tests/test_gpu_decode.py compares the two passes' reconstruction bytes, tests/test_gpu_recon_edges.py holds the tail to the reference's
+ * recorded bytes on coefficients the forward path never makes).  No inline assembly; every store is a vector store.
  *
  * Two launch forms: descriptor lists (svt_hip_recon_batch_device: svt_hip_tq_batch_device's svt_tq_block lists, eob per list entry) and
  * the encode pass's device-built position codes (svt_rc_launch_device_lists, used by svt_hip_decode_batch_device: a block's eob is read
@@ -39,11 +39,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? 4
                                                      const int16_t *__restrict__ qcoeff, const uint16_t *__restrict__ eob_in, uint16_t *__restrict__ eob_list,
                                                      uint32_t *__restrict__ overflow, const uint8_t *const *__restrict__ recon_set, tq_dev_count dc,
                                                      const uint8_t *__restrict__ eob_maps) {
-    if (dc.p) { /* device-built list: where this size's blocks start and how many there are */
-        const int o = dc.p[dc.s];
-        n_blocks = dc.p[4 + dc.s];
-        dc.pos += o; eob_list += o;
-    }
+    eob_list += dc.first_block(n_blocks); /* device-built list: where this size's blocks start and how many there are */
     constexpr int BPW = 256 / N;          /* blocks per workgroup */
     constexpr int LS  = N + 1;            /* padded LDS row stride in dwords */
     __shared__ int32_t tile[BPW][N * LS];
@@ -60,11 +56,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? 4
         int          eob = 0;
         if (dc.pos) { /* (uniform) the list holds position codes: the descriptor is rebuilt in registers */
             const uint32_t pc = dc.pos[active ? blk : 0];
-            const size_t   po = (size_t)svt_tq_pos_pic(pc) * dc.geom_stride;
-            const svt_tq_pic_geom *g = (const svt_tq_pic_geom *)(dc.geom + po);
-            svt_tq_block_from_pos(pc, txcfg<N>::size, g, dc.iscan_off, dc.sb_cols, &k);
+            const svt_tq_pic_geom *g = tq_block_of_pos<N>(dc, pc, &k);
             if (active) {
-                eob = rc_eob_of_pos(pc, g, *(const uint16_t *const *)(eob_maps + po));
+                eob = rc_eob_of_pos(pc, g, *(const uint16_t *const *)(eob_maps + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride));
                 if (i == 0) eob_list[blk] = (uint16_t)eob;
             }
         } else {
@@ -125,11 +119,8 @@ int32_t svt_rc_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_pred, uint
                                    const svt_quant_tables *d_qtabs, const int16_t *d_qcoeff, uint16_t *d_eob_list, const uint32_t *d_pos, const void *d_geom,
                                    const void *d_eob_maps, int geom_stride, const uint32_t *d_iscan_off, int sb_cols, uint32_t *d_overflow) {
     HIP_TRY(hipSetDevice(ctx->device));
-    void *h = nullptr, *d = nullptr; /* the reconstruction base pointers go to the device through the descriptor ring */
-    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "recon: descriptor buffers");
-    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr;
-    HIP_TRY(svt_ctx_stage_send(ctx, 8 * sizeof(void *)));
-    const uint8_t *const *d_set = (const uint8_t *const *)d;
+    const uint8_t *const *d_set = nullptr;
+    if (const int32_t e = tq_stage_recon_set(ctx, recon_set, n_set, &d_set)) return e;
     hipError_t rc = hipSuccess;
 #define RC_DEV(N, S) launch_rc<N>(ctx, d_pred, nullptr, nullptr, cap[S], d_qtabs, d_qcoeff, nullptr, d_eob_list, d_overflow, d_set, \
                                   tq_dev_count{d_off_cnt, S, d_pos, (const uint8_t *)d_geom, geom_stride, d_iscan_off, sb_cols}, (const uint8_t *)d_eob_maps)

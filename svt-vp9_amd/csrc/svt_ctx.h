@@ -104,6 +104,9 @@ int32_t svt_tq_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_src, const
                                    const svt_tq_block *d_blocks, const int32_t cap[4], const int32_t *d_off_cnt, const svt_quant_tables *d_qtabs,
                                    const int16_t *d_iscan, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, uint64_t *d_dist,
                                    const uint32_t *d_pos, const void *d_geom, int geom_stride, const uint32_t *d_iscan_off, int sb_cols);
+/* the (up to 8) reconstruction base pointers of a launch, staged through the descriptor ring: *d_set = the device copy, null beyond n_set
+ * (tq_kernel.hip; used by recon_kernel.hip too) */
+int32_t tq_stage_recon_set(svt_hip_ctx *ctx, uint8_t *const *recon_set, int n_set, const uint8_t *const **d_set);
 
 /* reconstruction from coefficients over device-built block lists (recon_kernel.hip; used by encdec.hip's decode pass) */
 int32_t svt_rc_launch_device_lists(svt_hip_ctx *ctx, const uint8_t *d_pred, uint8_t *const *recon_set, int n_set, const int32_t cap[4], const int32_t *d_off_cnt,

@@ -2,7 +2,9 @@
  * inverse transform -> reconstruction of ONE N x N block by N lanes of a wave, as perform_coding_loop does it
  * (Source/Lib/Codec/EbEncDecProcess.c:365-587; file comment of tq_kernel.hip).  Shared by the batch kernels (tq_kernel.hip: inter
  * pictures, prediction read from memory) and the intra kernel (intra_kernel.hip: prediction computed in registers from the
- * neighbours' reconstruction), so that there is one copy of every rounding rule.  Device code only; everything is internal linkage. */
+ * neighbours' reconstruction), so that there is one copy of every rounding rule: the quantiser (tq_load_qtab, tq_quant_coeff) is also the
+ * one of the block-per-lane 4x4 kernel (tq_kernel.hip), and the reconstruction half (tq_recon_tail) also the one of the decode pass
+ * (rc_core.h).  Device code only; everything is internal linkage. */
 #ifndef SVT_TQ_CORE_H
 #define SVT_TQ_CORE_H
 #include <hip/hip_runtime.h>
@@ -29,6 +31,15 @@ struct tq_dev_count {
     /* pos != null: the list is position codes (encdec_core.h: svt_tq_pos), not descriptors -- a block's descriptor is rebuilt from its code,
      * this launch's transform size and the picture's geometry record at geom + picture * geom_stride (svt_tq_block_from_pos) */
     const uint32_t *pos; const uint8_t *geom; int geom_stride; const uint32_t *iscan_off; int sb_cols;
+    /* a kernel's prologue: for a device-built list, sets n_blocks to this size's count, moves pos to its first block and returns that
+     * block's index (what the kernel adds to its per-block arrays); 0 and nothing changed for a list the host sized */
+    __device__ __forceinline__ int first_block(int &n_blocks) {
+        if (!p) return 0;
+        const int o = p[s];
+        n_blocks = p[4 + s];
+        if (pos) pos += o;
+        return o;
+    }
 };
 
 /* Workgroups are persistent and XCD-aware: workgroup w runs on XCD w & 7 (round-robin dispatch), and the groups of blocks it
@@ -72,13 +83,20 @@ template <int N> __device__ __forceinline__ uint32_t tq_lanes_sum(uint32_t v) {
  * tables (6 KB) per workgroup that left 5 (32x32) / 10 (16x16) waves per CU -- the stage was latency-bound by its own occupancy.
  * In the dependency-true step the transform stage's time on the GPU adds to the step 1:1, so the tables are shared by four
  * waves instead: 12 / 16 waves per CU, the stage alone 1.57 -> 1.32 ms per mini-GOP, the step 3.27 -> 3.17 ms. */
-template <int N, bool RATE> constexpr int tq_threads() { return 256; }
+constexpr int TQ_THREADS = 256;
 
 template <int N> struct txcfg;
 template <> struct txcfg<4> { static constexpr int size = SVT_TX_4X4, shift = 4; };
 template <> struct txcfg<8> { static constexpr int size = SVT_TX_8X8, shift = 5; };
 template <> struct txcfg<16> { static constexpr int size = SVT_TX_16X16, shift = 6; };
 template <> struct txcfg<32> { static constexpr int size = SVT_TX_32X32, shift = 6; };
+
+/* the descriptor of the N x N block with position code pc, rebuilt in registers (tq_dev_count::pos); returns its picture's geometry record */
+template <int N> __device__ __forceinline__ const svt_tq_pic_geom *tq_block_of_pos(const tq_dev_count &dc, uint32_t pc, svt_tq_block *k) {
+    const svt_tq_pic_geom *g = (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride);
+    svt_tq_block_from_pos(pc, txcfg<N>::size, g, dc.iscan_off, dc.sb_cols, k);
+    return g;
+}
 
 /* forward 1-D for the hybrid (vp9_dct.c) path: DCT outputs are stored to int16 */
 template <int N> __device__ __forceinline__ void fwd1d_hybrid(const int32_t *v, int32_t *o, bool adst) {
@@ -150,15 +168,115 @@ __device__ __forceinline__ void tq_block_sync() {
 __device__ __forceinline__ int clamp16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
 __device__ __forceinline__ uint8_t clip_add(int d, int t) { int v = d + t; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 
+/* quantiser table `idx`: the 20-byte record as five dwords instead of ten halfword loads */
+__device__ __forceinline__ svt_quant_tables tq_load_qtab(const svt_quant_tables *__restrict__ qtabs, const int idx) {
+    const uint32_t  *qp = (const uint32_t *)(qtabs + idx);
+    uint32_t         qw5[5];
+    svt_quant_tables q;
+    _Pragma("unroll") for (int j = 0; j < 5; j++) qw5[j] = qp[j];
+    q.zbin[0] = (int16_t)qw5[0]; q.zbin[1] = (int16_t)(qw5[0] >> 16); q.round[0] = (int16_t)qw5[1]; q.round[1] = (int16_t)(qw5[1] >> 16);
+    q.quant[0] = (int16_t)qw5[2]; q.quant[1] = (int16_t)(qw5[2] >> 16); q.quant_shift[0] = (int16_t)qw5[3]; q.quant_shift[1] = (int16_t)(qw5[3] >> 16);
+    q.dequant[0] = (int16_t)qw5[4]; q.dequant[1] = (int16_t)(qw5[4] >> 16);
+    return q;
+}
+
+/* eb_vp9_quantize_b (T32: eb_vp9_quantize_b_32x32; VPX/quantize.c:112-254) of one coefficient cv, ac = 0 for the block's DC: the level
+ * (unsigned, before the int16 cast), the quantised and the dequantised value */
+template <bool T32> __device__ __forceinline__ void tq_quant_coeff(const svt_quant_tables &q, const int ac, const int cv, int &level, int &qv, int &dv) {
+    const int sign = cv >> 31;
+    int       a = (cv ^ sign) - sign;
+    level = 0; qv = 0; dv = 0;
+    if constexpr (!T32) {
+        if (a >= q.zbin[ac]) {
+            const int tmp = clamp16(a + q.round[ac]);
+            level = ((((tmp * q.quant[ac]) >> 16) + tmp) * q.quant_shift[ac]) >> 16;
+            qv = (int16_t)((level ^ sign) - sign);
+            dv = (int16_t)(qv * q.dequant[ac]);
+        }
+    } else {
+        const int zbin = (q.zbin[ac] + 1) >> 1;
+        if (cv >= zbin || cv <= -zbin) {
+            a = clamp16(a + ((q.round[ac] + 1) >> 1));
+            level = ((((a * q.quant[ac]) >> 16) + a) * q.quant_shift[ac]) >> 15;
+            qv = (int16_t)((level ^ sign) - sign);
+            dv = (int16_t)(qv * q.dequant[ac] / 2);
+        }
+    }
+}
+
+/* The reconstruction half of a block, for the encode bodies (tq_block_body) and the decode ones (rc_block_body, rc_core.h): from the
+ * dequantised row dq of lane i (= vertical frequency i) and the block's eob to recon = clip(pred + inverse transform), rows first, then
+ * columns, with the eob shortcuts of vp9_idct.c (DC only; 4 / 8 / 16 rows of the larger transforms).  k: the block's descriptor (recon_off,
+ * recon_stride); active, i, t, prow as tq_block_body's; tx_type: already DCT_DCT for 32x32; recon_base + k.recon_off = the block's
+ * reconstruction (null: the block named a reconstruction set the caller did not pass).  The tile must be free when it is called (a caller
+ * that has used it puts a tq_block_sync in front) and is in use when it returns.
+ * WT: the reconstruction is stored write-through (agent-scope dword stores), for a caller whose neighbour blocks are read by other
+ * workgroups of the SAME launch (intra_kernel.hip, intra_recon_kernel.hip): they then see it without a release fence -- on this part an
+ * agent-scope release / acquire pair writes back / invalidates the whole L2 of the XCD, for every kernel running beside the caller.
+ * The tq_block_sync calls between the uses of the tile order the COMPILER: a wave's LDS accesses execute in the order they were issued, so
+ * the hardware needs no rendezvous, and none of them costs a wait or an instruction. */
+template <int N, bool WT>
+__device__ __forceinline__ void tq_recon_tail(const svt_tq_block &k, const bool active, const int i, int32_t *t, const uint32_t (&prow)[N / 4], const int32_t (&dq)[N],
+                                              const int tx_type, const int eob, uint8_t *recon_base) {
+    constexpr int LS = N + 1;            /* padded LDS row stride in dwords */
+    const bool col_adst = tx_type == SVT_ADST_DCT || tx_type == SVT_ADST_ADST;
+    const bool row_adst = tx_type == SVT_DCT_ADST || tx_type == SVT_ADST_ADST;
+    int32_t v[N], o[N], res[N];
+    _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = 0;
+    bool dc_only = false;
+    int  nrows = N;
+    if (tx_type == SVT_DCT_DCT) {
+        if (N == 4) dc_only = eob <= 1;
+        else dc_only = eob == 1;
+        if (N == 8) nrows = eob <= 12 ? 4 : 8;
+        if (N == 16) nrows = eob <= 10 ? 4 : eob <= 38 ? 8 : 16;
+        if (N == 32) nrows = eob <= 34 ? 8 : eob <= 135 ? 16 : 32;
+    }
+    if (eob != 0 && !dc_only) {
+        if (i < nrows) inv1d<N>(dq, o, row_adst);
+        else { _Pragma("unroll") for (int kk = 0; kk < N; kk++) o[kk] = 0; }
+        _Pragma("unroll") for (int kk = 0; kk < N; kk++) t[i * LS + kk] = (int16_t)o[kk];
+    } else if (eob != 0 && i == 0) {
+        t[0] = dq[0];
+    }
+    tq_block_sync();
+    if (eob != 0 && !dc_only) {
+        _Pragma("unroll") for (int r = 0; r < N; r++) v[r] = t[r * LS + i];
+        inv1d<N>(v, o, col_adst);
+        _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = ((int16_t)o[r] + (1 << (txcfg<N>::shift - 1))) >> txcfg<N>::shift;
+    } else if (eob != 0) {
+        /* eb_vp9_idct*_1_add_c: inv_txfm.c:174, 368, 784, 1241 */
+        int32_t d = tx_rsw((int16_t)t[0] * TX_C16);
+        d = tx_rsw(d * TX_C16);
+        const int32_t a1 = (d + (1 << (txcfg<N>::shift - 1))) >> txcfg<N>::shift;
+        _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = a1;
+    }
+    tq_block_sync(); /* (the DC lane's t[0] has been read) */
+    /* residual column i -> LDS -> row i; reconstruction = clip(pred row + residual row), stored as dwords */
+    _Pragma("unroll") for (int r = 0; r < N; r++) t[r * LS + i] = res[r];
+    tq_block_sync();
+    if (active && recon_base) {
+        uint8_t *d = recon_base + k.recon_off + (size_t)i * k.recon_stride;
+        uint32_t rw[N / 4];
+        _Pragma("unroll") for (int q = 0; q < N / 4; q++) {
+            uint32_t w = 0;
+            _Pragma("unroll") for (int b = 0; b < 4; b++)
+                w |= (uint32_t)clip_add((int)((prow[q] >> (8 * b)) & 0xff), t[i * LS + 4 * q + b]) << (8 * b);
+            rw[q] = w;
+        }
+        if constexpr (WT) {
+            _Pragma("unroll") for (int q = 0; q < N / 4; q++) __hip_atomic_store((uint32_t *)d + q, rw[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else row_store<N>(d, ((uintptr_t)d & (N >= 16 ? 15 : N - 1)) == 0, rw);
+    }
+}
+
 /* One block.  k: its descriptor; active: false for the idle slots of a partly filled workgroup (they run along, store nothing);
  * i: the lane's column (first pass) / row (second pass); t: the block's N x (N + 1) dword LDS tile; srow / prow: row i of source and
  * prediction, packed; eob_slot / dist_slot / bits_slot: where the block's results go (dist_slot may be null; bits_slot, rate_T, s_tc,
  * s_scan only with RATE); recon_base + k.recon_off = the block's reconstruction; dqcoeff may be null (the dequantised coefficients then
  * go from the quantiser to the inverse transform in registers and nowhere else).  Every lane of a wave has to call it (the block's lanes
  * meet in tq_block_sync), with k.do_recon uniform over the wave.  Returns the block's eob (every lane of the block). */
-/* WT: the reconstruction is stored write-through (agent-scope dword stores), for a caller whose neighbour blocks are read by other
- * workgroups of the SAME launch (intra_kernel.hip): they then see it without a release fence -- on this part an agent-scope release /
- * acquire pair writes back / invalidates the whole L2 of the XCD, for every kernel running beside the caller */
+/* WT: tq_recon_tail's */
 template <int N, bool RATE, bool DIST, bool WT = false>
 __device__ __forceinline__ int tq_block_body(const svt_tq_block &k, const bool active, const int i, int32_t *t, const uint32_t (&srow)[N / 4],
                                               const uint32_t (&prow)[N / 4], const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all,
@@ -219,15 +337,7 @@ __device__ __forceinline__ int tq_block_body(const svt_tq_block &k, const bool a
         }
     }
     /* ---- quantise row i; eob = 1 + max scan position of a non-zero level ---- */
-    svt_quant_tables q;
-    {   /* the 20-byte table as five dwords instead of ten halfword loads */
-        const uint32_t *qp = (const uint32_t *)(qtabs + k.qtab);
-        uint32_t        qw5[5];
-        _Pragma("unroll") for (int j = 0; j < 5; j++) qw5[j] = qp[j];
-        q.zbin[0] = (int16_t)qw5[0]; q.zbin[1] = (int16_t)(qw5[0] >> 16); q.round[0] = (int16_t)qw5[1]; q.round[1] = (int16_t)(qw5[1] >> 16);
-        q.quant[0] = (int16_t)qw5[2]; q.quant[1] = (int16_t)(qw5[2] >> 16); q.quant_shift[0] = (int16_t)qw5[3]; q.quant_shift[1] = (int16_t)(qw5[3] >> 16);
-        q.dequant[0] = (int16_t)qw5[4]; q.dequant[1] = (int16_t)(qw5[4] >> 16);
-    }
+    const svt_quant_tables q = tq_load_qtab(qtabs, k.qtab);
     /* row i of the inverse scan, fetched as dwords up front (its latency hides behind the transforms) */
     uint32_t isw[N / 2];
     {
@@ -242,24 +352,9 @@ __device__ __forceinline__ int tq_block_body(const svt_tq_block &k, const bool a
     uint32_t qw[VC / 2], dqw[VC / 2];
     int16_t *qo = qcoeff + k.coeff_off + i * N, *dqo = dqcoeff + k.coeff_off + i * N;
     _Pragma("unroll") for (int kk = 0; kk < N; kk++) {
-        const int ac = (i | kk) != 0, cv = c[kk], sign = cv >> 31;
-        int       a = (cv ^ sign) - sign, level = 0, qv = 0, dv = 0;
-        if constexpr (N < 32) {
-            if (a >= q.zbin[ac]) {
-                const int tmp = clamp16(a + q.round[ac]);
-                level = ((((tmp * q.quant[ac]) >> 16) + tmp) * q.quant_shift[ac]) >> 16;
-                qv = (int16_t)((level ^ sign) - sign);
-                dv = (int16_t)(qv * q.dequant[ac]);
-            }
-        } else {
-            const int zbin = (q.zbin[ac] + 1) >> 1;
-            if (cv >= zbin || cv <= -zbin) {
-                a = clamp16(a + ((q.round[ac] + 1) >> 1));
-                level = ((((a * q.quant[ac]) >> 16) + a) * q.quant_shift[ac]) >> 15;
-                qv = (int16_t)((level ^ sign) - sign);
-                dv = (int16_t)(qv * q.dequant[ac] / 2);
-            }
-        }
+        const int cv = c[kk];
+        int       level, qv, dv;
+        tq_quant_coeff<N == 32>(q, (i | kk) != 0, cv, level, qv, dv);
         dq[kk] = dv;
         /* full_distortion_kernel32bit (C_DEFAULT/EbPictureOperators_C.c:288-311): the difference goes through an int16_t
            parameter, the sums wrap in uint32_t */
@@ -303,57 +398,10 @@ __device__ __forceinline__ int tq_block_body(const svt_tq_block &k, const bool a
         bits = (int)tq_lanes_sum<N>((uint32_t)bits);
         if (active && i == 0) *bits_slot = bits;
     }
-    if (k.do_recon) { /* uniform within a size group (launcher contract): the barriers below stay workgroup-uniform */
-    /* ---- reconstruction: recon = pred + inverse transform (rows first, then columns) ---- */
-    int32_t res[N];
-    _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = 0;
-    const bool dct_path = tx_type == SVT_DCT_DCT;
-    bool dc_only = false;
-    int  nrows = N;
-    if (dct_path) {
-        if (N == 4) dc_only = eob <= 1;
-        else dc_only = eob == 1;
-        if (N == 8) nrows = eob <= 12 ? 4 : 8;
-        if (N == 16) nrows = eob <= 10 ? 4 : eob <= 38 ? 8 : 16;
-        if (N == 32) nrows = eob <= 34 ? 8 : eob <= 135 ? 16 : 32;
+    if (k.do_recon) { /* uniform within a size group (launcher contract) */
+        tq_block_sync(); /* tile is reused */
+        tq_recon_tail<N, WT>(k, active, i, t, prow, dq, tx_type, eob, recon_base);
     }
-    tq_block_sync(); /* tile is reused */
-    if (eob != 0 && !dc_only) {
-        if (i < nrows) inv1d<N>(dq, o, row_adst);
-        else { _Pragma("unroll") for (int kk = 0; kk < N; kk++) o[kk] = 0; }
-        _Pragma("unroll") for (int kk = 0; kk < N; kk++) t[i * LS + kk] = (int16_t)o[kk];
-    } else if (eob != 0 && i == 0) {
-        t[0] = dq[0];
-    }
-    tq_block_sync();
-    if (eob != 0 && !dc_only) {
-        _Pragma("unroll") for (int r = 0; r < N; r++) v[r] = t[r * LS + i];
-        inv1d<N>(v, o, col_adst);
-        _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = ((int16_t)o[r] + (1 << (txcfg<N>::shift - 1))) >> txcfg<N>::shift;
-    } else if (eob != 0) {
-        /* eb_vp9_idct*_1_add_c: inv_txfm.c:174, 368, 784, 1241 */
-        int32_t d = tx_rsw((int16_t)t[0] * TX_C16);
-        d = tx_rsw(d * TX_C16);
-        const int32_t a1 = (d + (1 << (txcfg<N>::shift - 1))) >> txcfg<N>::shift;
-        _Pragma("unroll") for (int r = 0; r < N; r++) res[r] = a1;
-    }
-    /* residual column i -> LDS -> row i; reconstruction = clip(pred row + residual row), stored as dwords */
-    _Pragma("unroll") for (int r = 0; r < N; r++) t[r * LS + i] = res[r];
-    if (active && recon_base) { /* (null: the block named a reconstruction set the caller did not pass) */
-        /* a batch may reconstruct into several buffers (reference pictures of different mini-GOPs): pad_[0] bits 4-6 name the one */
-        uint8_t *d = recon_base + k.recon_off + (size_t)i * k.recon_stride;
-        uint32_t rw[N / 4];
-        _Pragma("unroll") for (int q = 0; q < N / 4; q++) {
-            uint32_t w = 0;
-            _Pragma("unroll") for (int b = 0; b < 4; b++)
-                w |= (uint32_t)clip_add((int)((prow[q] >> (8 * b)) & 0xff), t[i * LS + 4 * q + b]) << (8 * b);
-            rw[q] = w;
-        }
-        if constexpr (WT) {
-            _Pragma("unroll") for (int q = 0; q < N / 4; q++) __hip_atomic_store((uint32_t *)d + q, rw[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else row_store<N>(d, ((uintptr_t)d & (N >= 16 ? 15 : N - 1)) == 0, rw);
-    }
-    } /* do_recon */
     return eob;
 }
 

@@ -70,16 +70,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? (
                                                      const int16_t *__restrict__ iscan_all, int16_t *__restrict__ qcoeff,
                                                      int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out,
                                                      uint64_t *__restrict__ dist_out, tq_rate_args ra, const uint8_t *const *__restrict__ recon_set, tq_dev_count dc) {
-    if (dc.p) { /* device-built list: where this size's blocks start and how many there are */
-        const int o = dc.p[dc.s];
-        n_blocks = dc.p[4 + dc.s];
+    {   /* device-built list: where this size's blocks start and how many there are */
+        const int o = dc.first_block(n_blocks);
         blocks += o; eob_out += o;
-        if (dc.pos) dc.pos += o;
         if (dist_out) dist_out += 2 * o;
         if constexpr (RATE) ra.bits += o;
     }
-    constexpr int NT  = tq_threads<N, RATE>();
-    constexpr int BPW = NT / N;           /* blocks per workgroup */
+    constexpr int BPW = TQ_THREADS / N;   /* blocks per workgroup */
     constexpr int LS  = N + 1;            /* padded LDS row stride in dwords */
     __shared__ int32_t tile[BPW][N * LS];
     /* RATE: the four token-cost slices [plane_type][is_inter] of this transform size, copied once per (persistent) workgroup */
@@ -93,9 +90,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? (
     __shared__ int16_t s_scan[RATE ? SCAN_N : 2];
     if constexpr (RATE) {
         const uint32_t *g = &ra.T->token_costs[txcfg<N>::size][0][0][0][0][0][0];
-        for (int j = threadIdx.x; j < 4 * RATE_SLICE; j += NT) s_tc[j] = g[j];
+        for (int j = threadIdx.x; j < 4 * RATE_SLICE; j += TQ_THREADS) s_tc[j] = g[j];
         const uint32_t *gs = (const uint32_t *)(ra.scan + rate_scan_offset(txcfg<N>::size, 0)); /* 4-byte aligned, even count */
-        for (int j = threadIdx.x; j < SCAN_N / 2; j += NT) ((uint32_t *)s_scan)[j] = gs[j];
+        for (int j = threadIdx.x; j < SCAN_N / 2; j += TQ_THREADS) ((uint32_t *)s_scan)[j] = gs[j];
         __syncthreads();
     }
     const int lb  = threadIdx.x / N;      /* block slot inside the workgroup */
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? (
     auto block_of = [&](auto POS, int gj, uint32_t pc, svt_tq_block &k) {
         const int blk = (wk.base + gj) * BPW + lb;
         if constexpr (decltype(POS)::value)
-            svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+            tq_block_of_pos<N>(dc, pc, &k);
         else k = blocks[blk < n_blocks ? blk : 0];
     };
     /* lane i fetches ROW i of source and prediction as dwords (coalesced: the N lanes of a block read N consecutive rows of N bytes);
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N == 32 ? (
             svt_tq_block k;
             if (dc.pos) { /* (uniform) the list holds position codes: the descriptor is rebuilt in registers */
                 const uint32_t pc = dc.pos[active ? blk : 0];
-                svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+                tq_block_of_pos<N>(dc, pc, &k);
             } else if (active) k = blocks[blk];
             else { k = blocks[0]; }
             int32_t *t = tile[lb];
@@ -228,65 +225,43 @@ __device__ __forceinline__ int rate_walk4(const int (&tok)[16], const int (&en)[
     return sum;
 }
 
-/* 4x4 (and, unused, 8x8) blocks: one block per lane.  With N lanes per block the small transforms are a sliver of the instruction
+/* 4x4 blocks: one block per lane (why not 8x8 too: launch_tq).  With N lanes per block the small transforms are a sliver of the instruction
  * stream (descriptor decode and table loads repeated in every lane, LDS transposes, shuffles for eob and distortion: ~125
  * VALU lane-operations per sample, as many as a 32x32 block); a lane that owns the whole block keeps its samples in
  * registers from the residual to the reconstruction, needs no LDS, no barrier and no cross-lane step.  Same arithmetic as
- * svt_tq_kernel<N>.  4x4: the fwd_txfm.c and vp9_dct.c forms of the DCT coincide (the int16 casts are no-ops at this size);
- * 8x8: they differ in the cast inside tx_fdct8 (vp9_dct.c:67-68), selected by the block's transform type.  The inverse
+ * svt_tq_kernel<N>: the fwd_txfm.c and vp9_dct.c forms of the DCT coincide (the int16 casts are no-ops at this size).  The inverse
  * always runs all rows (the reference's reduced variants are shortcuts with identical results).  Memory instructions per
- * block are unchanged (a lane issues the N row loads its N lanes issued). */
-/* the N rows of source and prediction of a block, packed, into the calling lane */
-template <int N>
-__device__ __forceinline__ void tq_lane_rows(const svt_tq_block &k, const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, uint32_t (&srow)[N][N / 4], uint32_t (&prow)[N][N / 4]) {
-    _Pragma("unroll") for (int r = 0; r < N; r++) {
-        const uint8_t *sp = src + k.src_off + (size_t)r * k.src_stride, *pp = pred + k.pred_off + (size_t)r * k.pred_stride;
-        if constexpr (N == 4) { srow[r][0] = *(const uint32_t *)sp; prow[r][0] = *(const uint32_t *)pp; }
-        else {
-            row_load<N>(sp, ((uintptr_t)sp & 7) == 0, srow[r]);
-            row_load<N>(pp, ((uintptr_t)pp & 7) == 0, prow[r]);
-        }
+ * block are unchanged (a lane issues the four row loads its four lanes issued). */
+/* the four rows of source and prediction of a block, packed, into the calling lane */
+__device__ __forceinline__ void tq_lane_rows(const svt_tq_block &k, const uint8_t *__restrict__ src, const uint8_t *__restrict__ pred, uint32_t (&srow)[4], uint32_t (&prow)[4]) {
+    _Pragma("unroll") for (int r = 0; r < 4; r++) {
+        srow[r] = *(const uint32_t *)(src + k.src_off + (size_t)r * k.src_stride);
+        prow[r] = *(const uint32_t *)(pred + k.pred_off + (size_t)r * k.pred_stride);
     }
 }
 
-/* one 4x4 (8x8) block, whole, in the calling lane: the body of svt_tq_lane_kernel.  srow / prow: its rows (tq_lane_rows) */
-template <int N, bool RATE, bool DIST>
-__device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int blk, const uint32_t (&srow)[N][N / 4], const uint32_t (&prow)[N][N / 4], uint8_t *__restrict__ recon,
+/* one 4x4 block, whole, in the calling lane: the body of svt_tq_lane_kernel.  srow / prow: its rows (tq_lane_rows) */
+template <bool RATE, bool DIST>
+__device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int blk, const uint32_t (&srow)[4], const uint32_t (&prow)[4], uint8_t *__restrict__ recon,
                                               const svt_quant_tables *__restrict__ qtabs, const int16_t *__restrict__ iscan_all, int16_t *__restrict__ qcoeff,
                                               int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out, uint64_t *__restrict__ dist_out, const tq_rate_args &ra,
                                               const uint32_t *s_tc, const int32_t *s_vc, const uint8_t *const *__restrict__ recon_set) {
-    constexpr int ND = N / 4; /* dwords per row of samples */
+    constexpr int N = 4;
     const bool col_adst = k.tx_type == SVT_ADST_DCT || k.tx_type == SVT_ADST_ADST;
     const bool row_adst = k.tx_type == SVT_DCT_ADST || k.tx_type == SVT_ADST_ADST;
-    const bool dct_dct  = k.tx_type == SVT_DCT_DCT;
     int32_t    m[N][N]; /* after the column pass: m[kk][cc] = vertical frequency kk of column cc */
     {
         _Pragma("unroll") for (int cc = 0; cc < N; cc++) {
             int32_t v[N], o[N];
-            _Pragma("unroll") for (int r = 0; r < N; r++)
-                v[r] = ((int)((srow[r][cc >> 2] >> (8 * (cc & 3))) & 0xff) - (int)((prow[r][cc >> 2] >> (8 * (cc & 3))) & 0xff)) * (N == 4 ? 16 : 4);
-            if constexpr (N == 4) {
-                if (cc == 0 && v[0]) ++v[0];
-                if (col_adst) tx_fadst4(v, o); else tx_fdct4(v, o);
-            } else {
-                if (col_adst) tx_adst8(v, o);
-                else if (dct_dct) tx_fdct8(v, o, 0);
-                else tx_fdct8(v, o, 1);
-            }
+            _Pragma("unroll") for (int r = 0; r < N; r++) v[r] = ((int)((srow[r] >> (8 * cc)) & 0xff) - (int)((prow[r] >> (8 * cc)) & 0xff)) * 16;
+            if (cc == 0 && v[0]) ++v[0];
+            if (col_adst) tx_fadst4(v, o); else tx_fdct4(v, o);
             _Pragma("unroll") for (int kk = 0; kk < N; kk++) m[kk][cc] = (int16_t)o[kk];
         }
     }
     /* quantiser tables of the block (lanes of one table read the same addresses) */
-    svt_quant_tables q;
-    {
-        const uint32_t *qp = (const uint32_t *)(qtabs + k.qtab);
-        uint32_t        qw5[5];
-        _Pragma("unroll") for (int j = 0; j < 5; j++) qw5[j] = qp[j];
-        q.zbin[0] = (int16_t)qw5[0]; q.zbin[1] = (int16_t)(qw5[0] >> 16); q.round[0] = (int16_t)qw5[1]; q.round[1] = (int16_t)(qw5[1] >> 16);
-        q.quant[0] = (int16_t)qw5[2]; q.quant[1] = (int16_t)(qw5[2] >> 16); q.quant_shift[0] = (int16_t)qw5[3]; q.quant_shift[1] = (int16_t)(qw5[3] >> 16);
-        q.dequant[0] = (int16_t)qw5[4]; q.dequant[1] = (int16_t)(qw5[4] >> 16);
-    }
-    /* ---- row pass, quantisation, distortion, eob; each row of coefficients leaves as one 8/16-byte vector ---- */
+    const svt_quant_tables q = tq_load_qtab(qtabs, k.qtab);
+    /* ---- row pass, quantisation, distortion, eob; each row of coefficients leaves as one 8-byte vector ---- */
     int32_t  dq[N][N];
     uint32_t rdist = 0, pdist = 0;
     int      eob = 0;
@@ -296,26 +271,12 @@ __device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int b
         int32_t  o[N];
         uint32_t isw[N / 2], qw[N / 2], dqw[N / 2];
         _Pragma("unroll") for (int j = 0; j < N / 2; j++) isw[j] = ip[i * (N / 2) + j];
-        if constexpr (N == 4) {
-            if (row_adst) tx_fadst4(m[i], o);
-            else { tx_fdct4(m[i], o); _Pragma("unroll") for (int kk = 0; kk < N; kk++) o[kk] = (int16_t)o[kk]; }
-        } else {
-            if (row_adst) tx_adst8(m[i], o);
-            else {
-                if (dct_dct) tx_fdct8(m[i], o, 0); else tx_fdct8(m[i], o, 1);
-                _Pragma("unroll") for (int kk = 0; kk < N; kk++) o[kk] = (int16_t)o[kk];
-            }
-        }
+        if (row_adst) tx_fadst4(m[i], o);
+        else { tx_fdct4(m[i], o); _Pragma("unroll") for (int kk = 0; kk < N; kk++) o[kk] = (int16_t)o[kk]; }
         _Pragma("unroll") for (int kk = 0; kk < N; kk++) {
-            const int cv = N == 4 ? (int16_t)((o[kk] + 1) >> 2) : (int16_t)((o[kk] + (o[kk] < 0)) >> 1);
-            const int ac = (i | kk) != 0, sign = cv >> 31, a = (cv ^ sign) - sign;
-            int       level = 0, qv = 0, dv = 0;
-            if (a >= q.zbin[ac]) {
-                const int tmp = clamp16(a + q.round[ac]);
-                level = ((((tmp * q.quant[ac]) >> 16) + tmp) * q.quant_shift[ac]) >> 16;
-                qv = (int16_t)((level ^ sign) - sign);
-                dv = (int16_t)(qv * q.dequant[ac]);
-            }
+            const int cv = (int16_t)((o[kk] + 1) >> 2);
+            int       level, qv, dv;
+            tq_quant_coeff<false>(q, (i | kk) != 0, cv, level, qv, dv);
             dq[i][kk] = dv;
             if constexpr (DIST) {
                 const int dd = (int16_t)(cv - dv);
@@ -344,8 +305,8 @@ __device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int b
             }
         }
         int16_t *qo = qcoeff + k.coeff_off + i * N, *dqo = dqcoeff + k.coeff_off + i * N;
-        if constexpr (N == 4) { *(uint2 *)qo = make_uint2(qw[0], qw[1]); if (dqcoeff) *(uint2 *)dqo = make_uint2(dqw[0], dqw[1]); }
-        else { *(uint4 *)qo = make_uint4(qw[0], qw[1], qw[2], qw[3]); if (dqcoeff) *(uint4 *)dqo = make_uint4(dqw[0], dqw[1], dqw[2], dqw[3]); }
+        *(uint2 *)qo = make_uint2(qw[0], qw[1]);
+        if (dqcoeff) *(uint2 *)dqo = make_uint2(dqw[0], dqw[1]);
     }
     eob_out[blk] = (uint16_t)eob;
     if constexpr (DIST) if (dist_out) { dist_out[2 * blk] = rdist; dist_out[2 * blk + 1] = pdist; }
@@ -361,49 +322,41 @@ __device__ __forceinline__ void tq_lane_block(const svt_tq_block &k, const int b
         ra.bits[blk] = bits + vsum + (eob - nnz) * s_vc[66];
     }
     if (!k.do_recon) return;
-    /* ---- reconstruction: rows first, then columns (vp9_idct.c:111-189, inv_txfm.c); a column's eight results go straight
+    /* ---- reconstruction: rows first, then columns (vp9_idct.c:111-189, inv_txfm.c); a column's four results go straight
      * into the packed output rows ---- */
     constexpr int SH = txcfg<N>::shift;
-    uint32_t      rw[N][ND];
-    _Pragma("unroll") for (int r = 0; r < N; r++) { _Pragma("unroll") for (int j = 0; j < ND; j++) rw[r][j] = 0; }
-    const bool dc_only = dct_dct && (N == 4 ? eob <= 1 : eob == 1);
+    uint32_t      rw[N] = {0, 0, 0, 0};
+    const bool dc_only = k.tx_type == SVT_DCT_DCT && eob <= 1;
     if (eob != 0 && !dc_only) {
         int32_t t[N][N];
         _Pragma("unroll") for (int i = 0; i < N; i++) {
             int32_t o[N];
-            if constexpr (N == 4) { if (row_adst) tx_iadst4(dq[i], o); else tx_idct4(dq[i], o); }
-            else { if (row_adst) tx_adst8(dq[i], o); else tx_idct8(dq[i], o); }
+            inv1d<N>(dq[i], o, row_adst);
             _Pragma("unroll") for (int kk = 0; kk < N; kk++) t[i][kk] = (int16_t)o[kk];
         }
         _Pragma("unroll") for (int cc = 0; cc < N; cc++) {
             int32_t v[N], o[N];
             _Pragma("unroll") for (int r = 0; r < N; r++) v[r] = t[r][cc];
-            if constexpr (N == 4) { if (col_adst) tx_iadst4(v, o); else tx_idct4(v, o); }
-            else { if (col_adst) tx_adst8(v, o); else tx_idct8(v, o); }
+            inv1d<N>(v, o, col_adst);
             _Pragma("unroll") for (int r = 0; r < N; r++) {
                 const int res = ((int16_t)o[r] + (1 << (SH - 1))) >> SH;
-                rw[r][cc >> 2] |= (uint32_t)clip_add((int)((prow[r][cc >> 2] >> (8 * (cc & 3))) & 0xff), res) << (8 * (cc & 3));
+                rw[r] |= (uint32_t)clip_add((int)((prow[r] >> (8 * cc)) & 0xff), res) << (8 * cc);
             }
         }
     } else {
         int32_t a1 = 0;
-        if (eob != 0) { /* eb_vp9_idct4x4_1_add_c / idct8x8_1_add_c, inv_txfm.c:174, 368 */
+        if (eob != 0) { /* eb_vp9_idct4x4_1_add_c, inv_txfm.c:174 */
             int32_t d = tx_rsw((int16_t)dq[0][0] * TX_C16);
             d = tx_rsw(d * TX_C16);
             a1 = (d + (1 << (SH - 1))) >> SH;
         }
         _Pragma("unroll") for (int r = 0; r < N; r++) {
-            _Pragma("unroll") for (int cc = 0; cc < N; cc++)
-                rw[r][cc >> 2] |= (uint32_t)clip_add((int)((prow[r][cc >> 2] >> (8 * (cc & 3))) & 0xff), a1) << (8 * (cc & 3));
+            _Pragma("unroll") for (int cc = 0; cc < N; cc++) rw[r] |= (uint32_t)clip_add((int)((prow[r] >> (8 * cc)) & 0xff), a1) << (8 * cc);
         }
     }
     uint8_t *const rbase = recon_set ? (uint8_t *)recon_set[(k.pad_[0] >> 4) & 7] : recon;
     if (!rbase) return; /* a set index beyond the caller's n_set: nowhere to reconstruct to (never buffer 0 by default) */
-    _Pragma("unroll") for (int r = 0; r < N; r++) {
-        uint8_t *d = rbase + k.recon_off + (size_t)r * k.recon_stride;
-        if constexpr (N == 4) *(uint32_t *)d = rw[r][0];
-        else row_store<N>(d, ((uintptr_t)d & 7) == 0, rw[r]);
-    }
+    _Pragma("unroll") for (int r = 0; r < N; r++) *(uint32_t *)(rbase + k.recon_off + (size_t)r * k.recon_stride) = rw[r];
 }
 
 template <int N, bool RATE, bool DIST>
@@ -413,16 +366,13 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
                                                           const int16_t *__restrict__ iscan_all, int16_t *__restrict__ qcoeff,
                                                           int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob_out,
                                                           uint64_t *__restrict__ dist_out, tq_rate_args ra, const uint8_t *const *__restrict__ recon_set, tq_dev_count dc) {
-    if (dc.p) {
-        const int o = dc.p[dc.s];
-        n_blocks = dc.p[4 + dc.s];
+    static_assert(N == 4, "block-per-lane form: 4x4 only (launch_tq)");
+    {   /* device-built list (svt_tq_kernel) */
+        const int o = dc.first_block(n_blocks);
         blocks += o; eob_out += o;
-        if (dc.pos) dc.pos += o;
         if (dist_out) dist_out += 2 * o;
         if constexpr (RATE) ra.bits += o;
     }
-    static_assert(N == 4 || N == 8, "block-per-lane form: 4x4 and 8x8 only");
-    static_assert(!RATE || N == 4, "in-lane rate: 4x4 only");
     /* RATE: the four 4x4 token-cost slices [plane_type][is_inter] and the value-cost table, copied once per workgroup */
     __shared__ uint32_t s_tc[RATE ? 4 * RATE_SLICE : 1];
     __shared__ int32_t  s_vc[RATE ? 136 : 1];
@@ -439,7 +389,7 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
     auto blk_of = [&](int gj) { return (wk.base + gj) * 256 + (int)threadIdx.x; };
     auto in_walk = [&](int gj) { return gj < wk.per_xcd && blk_of(gj) < n_blocks; };
     auto block_of = [&](auto POS, int gj, uint32_t pc, svt_tq_block &k) {
-        if constexpr (decltype(POS)::value) svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+        if constexpr (decltype(POS)::value) tq_block_of_pos<N>(dc, pc, &k);
         else k = blocks[blk_of(gj)];
     };
     if constexpr (!tq_pipelined<N, RATE, DIST>()) { /* the serial walk: fetch, then compute */
@@ -449,11 +399,11 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
         svt_tq_block k;
         if (dc.pos) {
             const uint32_t pc = dc.pos[blk];
-            svt_tq_block_from_pos(pc, txcfg<N>::size, (const svt_tq_pic_geom *)(dc.geom + (size_t)svt_tq_pos_pic(pc) * dc.geom_stride), dc.iscan_off, dc.sb_cols, &k);
+            tq_block_of_pos<N>(dc, pc, &k);
         } else k = blocks[blk];
-        uint32_t srow[N][N / 4], prow[N][N / 4];
-        tq_lane_rows<N>(k, src, pred, srow, prow);
-        tq_lane_block<N, RATE, DIST>(k, blk, srow, prow, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
+        uint32_t srow[4], prow[4];
+        tq_lane_rows(k, src, pred, srow, prow);
+        tq_lane_block<RATE, DIST>(k, blk, srow, prow, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
       }
       return;
     }
@@ -461,21 +411,21 @@ __global__ __launch_bounds__(256) void svt_tq_lane_kernel(const uint8_t *__restr
         constexpr bool P = decltype(POS)::value;
         int      gj = wk.first;
         bool     have0 = in_walk(gj), have1 = have0 && in_walk(gj + wk.step);
-        uint32_t pc0 = 0u, pc1 = 0u, s0[N][N / 4] = {}, p0[N][N / 4] = {};
+        uint32_t pc0 = 0u, pc1 = 0u, s0[4] = {}, p0[4] = {};
         if constexpr (P) { if (have0) pc0 = dc.pos[blk_of(gj)]; if (have1) pc1 = dc.pos[blk_of(gj + wk.step)]; }
-        if (have0) { svt_tq_block k; block_of(POS, gj, pc0, k); tq_lane_rows<N>(k, src, pred, s0, p0); }
+        if (have0) { svt_tq_block k; block_of(POS, gj, pc0, k); tq_lane_rows(k, src, pred, s0, p0); }
         while (have0) {
             const int  g1 = gj + wk.step, g2 = g1 + wk.step;
             const bool have2 = have1 && in_walk(g2);
-            uint32_t   pc2 = 0u, s1[N][N / 4] = {}, p1[N][N / 4] = {};
+            uint32_t   pc2 = 0u, s1[4] = {}, p1[4] = {};
             svt_tq_block k, kn; /* this block's descriptor, whole, and the address fields of the lane's next (svt_tq_kernel) */
             block_of(POS, gj, pc0, k);
             block_of(POS, have1 ? g1 : gj, have1 ? pc1 : pc0, kn);
             tq_loads_landed();
-            if (have1) tq_lane_rows<N>(kn, src, pred, s1, p1);
+            if (have1) tq_lane_rows(kn, src, pred, s1, p1);
             if constexpr (P) { if (have2) pc2 = dc.pos[blk_of(g2)]; }
-            tq_lane_block<N, RATE, DIST>(k, blk_of(gj), s0, p0, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
-            _Pragma("unroll") for (int r = 0; r < N; r++) { _Pragma("unroll") for (int q = 0; q < N / 4; q++) { s0[r][q] = s1[r][q]; p0[r][q] = p1[r][q]; } }
+            tq_lane_block<RATE, DIST>(k, blk_of(gj), s0, p0, recon, qtabs, iscan_all, qcoeff, dqcoeff, eob_out, dist_out, ra, s_tc, s_vc, recon_set);
+            _Pragma("unroll") for (int r = 0; r < 4; r++) { s0[r] = s1[r]; p0[r] = p1[r]; }
             pc0 = pc1; pc1 = pc2; gj = g1; have0 = have1; have1 = have2;
         }
     };
@@ -514,21 +464,11 @@ hipError_t launch_tq(svt_hip_ctx *ctx, const uint8_t *src, const uint8_t *pred, 
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     } else {
-        constexpr int NT = tq_threads<N, RATE>(), BPW = NT / N;
-        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, per_2cu, txcfg<N>::size)), dim3(NT), 0, ctx->stream, src, pred, recon, blocks, n, q,
+        constexpr int BPW = TQ_THREADS / N;
+        hipLaunchKernelGGL((svt_tq_kernel<N, RATE, DIST>), dim3(tq_grid(ctx, (n + BPW - 1) / BPW, per_2cu, txcfg<N>::size)), dim3(TQ_THREADS), 0, ctx->stream, src, pred, recon, blocks, n, q,
                            iscan, qc, dqc, eob, dist, ra, recon_set, dc);
         return hipGetLastError();
     }
-}
-
-/* several reconstruction buffers: their base pointers go to the device through the descriptor ring */
-int32_t tq_stage_recon_set(svt_hip_ctx *ctx, uint8_t *const *recon_set, int n_set, const uint8_t *const **d_set) {
-    void *h = nullptr, *d = nullptr;
-    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
-    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr; /* a block that names a set >= n_set is not reconstructed anywhere */
-    HIP_TRY(svt_ctx_stage_send(ctx, 8 * sizeof(void *)));
-    *d_set = (const uint8_t *const *)d;
-    return SVT_HIP_OK;
 }
 
 template <bool RATE>
@@ -556,6 +496,17 @@ int32_t tq_launch_all(svt_hip_ctx *ctx, const uint8_t *d_src, const uint8_t *d_p
     return SVT_HIP_OK;
 }
 } // namespace
+
+/* several reconstruction buffers: their base pointers go to the device through the descriptor ring.  Internal to the library (declared in
+ * svt_ctx.h; recon_kernel.hip stages its set with it too). */
+int32_t tq_stage_recon_set(svt_hip_ctx *ctx, uint8_t *const *recon_set, int n_set, const uint8_t *const **d_set) {
+    void *h = nullptr, *d = nullptr;
+    if (svt_ctx_stage(ctx, 8 * sizeof(void *), &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "tq: descriptor buffers");
+    for (int i = 0; i < 8; i++) ((uint8_t **)h)[i] = i < n_set ? recon_set[i] : nullptr; /* a block that names a set >= n_set is not reconstructed anywhere */
+    HIP_TRY(svt_ctx_stage_send(ctx, 8 * sizeof(void *)));
+    *d_set = (const uint8_t *const *)d;
+    return SVT_HIP_OK;
+}
 
 /* Transform stage over block lists that were built ON THE DEVICE (csrc/encdec.hip): d_off_cnt[s] / d_off_cnt[4 + s] = first block and
  * number of blocks of size s inside d_blocks / d_eob; cap[s] = an upper bound known to the host, which only sizes the persistent
