@@ -779,7 +779,7 @@ int32_t svt_hip_coeff_rate_batch(svt_hip_ctx *ctx, const int16_t *qcoeff, size_t
  *   prob_row  (((tx_size * 2 + plane_type) * 2 + is_inter) * 6 + band) * 6 + ctx (< 576): TOKENEXTRA.context_tree =
  *             &coef_probs[0][0][0][0][0][0] + 3 * prob_row
  * counts[SVT_TOK_COUNTS] = td->rd_counts.coef_counts[tx_size][plane_type][is_inter][band][ctx][token] = counts[prob_row * 12 + token]
- * (eob_branch is compiled out in the reference and is not produced). */
+ * (eob_branch is compiled out in the reference and is not produced here: svt_hip_coef_update_batch_device counts it from the records). */
 #define SVT_TOK_EOB 11
 #define SVT_TOK_COUNTS 6912   /* 4 * 2 * 2 * 6 * 6 * 12 */
 #define SVT_TOK_NONE 0xFFFFFFFFu
@@ -904,6 +904,89 @@ uint32_t svt_hip_boolcode_capacity(uint32_t n_bools);
 uint32_t svt_hip_boolcode_bools_capacity(uint32_t n_tokens);
 /* the kernels' constants: bools per chunk (K) and chunks per tile of the chain kernel */
 void svt_hip_boolcode_geometry(int32_t *bools_per_chunk, int32_t *chunks_per_tile);
+/* svt_hip_boolcode_batch_device with coefficient probabilities per stream: d_coef_probs is a HOST array of n_streams DEVICE pointers to
+ * 1 728 bytes each ([prob_row][node], e.g. svt_cu_picture.d_probs); a NULL entry (or d_coef_probs NULL) means the context's table.  pareto
+ * and cat_probs are the context's for every stream.  The same kernels; the expand kernel alone reads the table and is instantiated twice,
+ * so the entry above runs the code it ran before this one existed. */
+int32_t svt_hip_boolcode_batch_tables_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams, const uint8_t *const *d_coef_probs);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Forward coefficient-probability update: a picture's token stream and coef_counts -> the coefficient section of its compressed header
+ * (as bool records, between the records in front of and behind it) and the probabilities its tile is then coded with.
+ *
+ * Replaces update_coef_probs (VPX/vp9_bitstream.c:669-687).  The reference leaves FRAME_COUNTS zeroed and so writes one "no update" bit
+ * per transform size; its update code is alive and is what this stage restates (rules: csrc/coef_update_core.h): build_tree_distribution
+ * with eob_branch counted from the token stream, the TWO_LOOP decision per transform size, the savings searches and the
+ * sub-exponential code of VPX/vp9_subexp.c with coeff_prob_appx_step 1.  All sums are 64-bit: equal to the reference wherever its 32-bit
+ * sums do not wrap (a branch count of about 2^31 / 4096), true beyond.
+ *
+ *   d_tokens       the picture's token records in stream order (svt_hip_tokenize_batch_device's d_tokens), scanned as ONE run
+ *   d_n_tokens     device count of them (the last entry of the tokeniser's d_sb_off), or NULL: n_tokens.  max_tokens sizes the count
+ *                  kernel's grid and bounds the scan: records at or beyond it are not read
+ *   d_counts       SVT_TOK_COUNTS coef_counts (the tokeniser's d_counts)
+ *   d_old_probs    1 728 bytes the update is measured against and coded relative to; NULL: the coef_probs of the context's
+ *                  svt_hip_boolcode_set_tables table.  Callers that code every picture from the default probabilities and send
+ *                  refresh_frame_context = 0 (all of today's) leave it NULL: the pictures of a batch are then independent.  Chaining
+ *                  pictures (refresh_frame_context = 1) is a later change and needs only this pointer.  Entries are 1 .. 255; a 0 is read as 1
+ *   d_eob_branch   576 counts, overwritten: records of prob_row r that code node 0
+ *   d_probs        1 728 bytes, overwritten: the probabilities after the update (the old ones where nothing is sent)
+ *   d_hdr_bools    the compressed header's complete record list prefix || coefficient section || suffix, svt_hip_coef_update_bools_capacity()
+ *                  records; *d_n_hdr_bools = their number; *d_segment = {0, n, 1}: svt_hip_boolcode_batch_device codes the header as a
+ *                  bool-only stream (d_bools = d_hdr_bools, d_segments = d_segment, n_segments = 1)
+ *   prefix, suffix the records in front of and behind the section (svt_hip_frame_header_parts_host); they travel inside the descriptor
+ *   d_result       svt_cu_result: per transform size the entries that update (counted also when the size is not sent), whether the size
+ *                  is sent, its summed savings in 1/512 bit as the decision saw them (0 for a size with tx_total <= 20); the header's bools
+ * sizeof(svt_cu_picture) = 528, sizeof(svt_cu_result) = 72. */
+#define SVT_CU_ROWS 576
+#define SVT_CU_PROBS 1728
+#define SVT_CU_ENTRIES 396          /* per transform size: 132 rows that exist x 3 nodes */
+#define SVT_CU_MAX_PER_ENTRY 12     /* the flag, 3 bits of the range, 7 + 1 bits of encode_uniform */
+#define SVT_CU_SECTION_MAX (4 * (1 + SVT_CU_ENTRIES * SVT_CU_MAX_PER_ENTRY))
+#define SVT_CU_PREFIX_MAX 8
+#define SVT_CU_SUFFIX_MAX 208
+#define SVT_CU_MAX_PICS 32
+typedef struct svt_cu_result {
+    uint32_t updated[4];
+    uint32_t sent[4];
+    uint32_t hdr_bools;
+    uint32_t tokens;       /* records scanned */
+    int64_t  savings[4];
+} svt_cu_result;
+typedef struct svt_cu_picture {
+    const uint32_t   *d_tokens;
+    const uint32_t   *d_n_tokens;
+    const uint32_t   *d_counts;
+    const uint8_t    *d_old_probs;
+    uint32_t         *d_eob_branch;
+    uint8_t          *d_probs;
+    uint16_t         *d_hdr_bools;
+    uint32_t         *d_n_hdr_bools;
+    svt_bool_segment *d_segment;
+    svt_cu_result    *d_result;
+    uint32_t          n_tokens, max_tokens;
+    uint16_t          n_prefix, n_suffix;
+    uint16_t          prefix[SVT_CU_PREFIX_MAX];
+    uint16_t          suffix[SVT_CU_SUFFIX_MAX];
+    uint32_t          pad_;
+} svt_cu_picture;
+/* n_pics (<= SVT_CU_MAX_PICS) pictures in one call (host array of descriptors holding device pointers): the count kernel (an LDS
+ * histogram per workgroup, partial histograms in a context buffer, no global atomics), the decide kernel (one workgroup per picture and
+ * transform size) and the kernel that joins the sections.  Asynchronous on the context's stream: behind svt_hip_tokenize_batch_device
+ * and in front of svt_hip_boolcode_batch_tables_device it needs no host round trip.  Refused, with nothing launched: a null pointer
+ * (d_n_tokens and d_old_probs may be NULL; d_tokens may be NULL when max_tokens is 0), n_pics out of range, n_prefix / n_suffix beyond
+ * their arrays, svt_hip_boolcode_set_tables not called. */
+int32_t svt_hip_coef_update_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_cu_picture *pics);
+/* host form of the same text (csrc/coef_update_core.h), pure CPU; the svt_cu_picture fields are host pointers; d_old_probs NULL:
+ * tables->coef_probs */
+int32_t svt_hip_coef_update_picture(const svt_cu_picture *pic, const svt_bool_tables *tables);
+/* records d_hdr_bools must hold: SVT_CU_PREFIX_MAX + SVT_CU_SECTION_MAX + SVT_CU_SUFFIX_MAX */
+uint32_t svt_hip_coef_update_bools_capacity(void);
+/* the count kernel's constants: records per workgroup and pass, workgroups of a picture at most */
+void svt_hip_coef_update_geometry(int32_t *records_per_pass, int32_t *max_workgroups);
+/* the tables behind the rules, for tests: the 256 probability costs (eb_vp9_prob_cost); remap[(newp - 1) * 255 + oldp - 1] for all 255 x 255
+ * pairs (0 on the diagonal) and bits[] likewise, the bools the update of that pair writes */
+const uint16_t *svt_hip_coef_update_cost_table(void);
+void svt_hip_coef_update_remap_tables(uint8_t *remap, uint8_t *bits);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Key-frame mode-info syntax: the grid of an intra-only picture -> the raw bools and the segment list that, with the tokeniser's
@@ -1529,6 +1612,15 @@ typedef struct svt_frame_params {
  * filter_level or sharpness_level out of its bit width; intra_only together with show_frame on a non-key frame (the bit is not coded
  * then); a capacity below the bytes needed (SVT_FRAME_HEADER_MAX always suffices). */
 int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes, uint32_t *compressed_bytes);
+/* The same two headers around a coefficient section that updates (svt_hip_coef_update_batch_device / svt_hip_coef_update_picture).
+ * svt_hip_frame_header_parts_host yields the bool records of the compressed header in front of the section (at most SVT_CU_PREFIX_MAX)
+ * and behind it (at most SVT_CU_SUFFIX_MAX), from the text svt_hip_frame_header_host writes them with.  svt_hip_frame_header_coef_host
+ * writes the uncompressed header as above and codes the compressed header from the complete record list hdr_bools (prefix || section ||
+ * suffix) with svt_hip_boolcode_host; first_part_size is the coder's answer.  With a section of four "no update" bits the bytes are
+ * svt_hip_frame_header_host's.  Refused as above; a capacity below the bytes needed writes nothing the caller may use. */
+int32_t svt_hip_frame_header_parts_host(const svt_frame_params *p, uint16_t *prefix, uint32_t *n_prefix, uint16_t *suffix, uint32_t *n_suffix);
+int32_t svt_hip_frame_header_coef_host(const svt_frame_params *p, const uint16_t *hdr_bools, uint32_t n_hdr_bools, uint8_t *out, uint32_t capacity,
+                                       uint32_t *uncompressed_bytes, uint32_t *compressed_bytes);
 /* the one-byte frame that shows DPB slot dpb_slot (0 .. 7): eb_vp9_pack_bitstream with show_existing_frame set */
 int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out);
 
@@ -1568,6 +1660,12 @@ typedef struct svt_frame_read_info {
 } svt_frame_read_info;                  /* 80 bytes */
 int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
                                        svt_frame_read_info *info);
+/* the same reader for frames whose compressed header updates coefficient probabilities: the updates are read (the inverse of the remap
+ * and of the sub-exponential code, csrc/coef_update_core.h) and applied to tables_inout->coef_probs, which enters as the table the
+ * update was coded against and leaves as the table the tile is coded with (svt_hip_tile_read_host takes it).  Every other update flag is
+ * refused as above; the two readers above and svt_hip_frame_read_host keep refusing a coefficient update too. */
+int32_t svt_hip_frame_read_header_coef_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
+                                            svt_frame_read_info *info, svt_bool_tables *tables_inout);
 
 /* The tile of a KEY FRAME read back (host/frame_read.c): the inverse of svt_hip_modes_kf_picture, svt_hip_tokenize_picture and the bool
  * coder, block by block in coding order -- partition walk, skip flag, intra modes, tokens (the Pareto tail, category bits MSB first,

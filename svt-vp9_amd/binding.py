@@ -170,6 +170,22 @@ class BoolStream(C.Structure):
                 ("n_tokens", C.c_uint32), ("max_bools", C.c_uint32), ("capacity", C.c_uint32), ("d_bytes", C.c_void_p), ("d_size", C.c_void_p)]
 
 
+# forward coefficient-probability update (svt_cu_result / svt_cu_picture of include/svtvp9_hip.h)
+CU_ROWS, CU_PROBS, CU_ENTRIES, CU_MAX_PER_ENTRY, CU_PREFIX_MAX, CU_SUFFIX_MAX, CU_MAX_PICS = 576, 1728, 396, 12, 8, 208, 32
+CU_SECTION_MAX = 4 * (1 + CU_ENTRIES * CU_MAX_PER_ENTRY)
+CU_RESULT_DTYPE = np.dtype([("updated", "<u4", (4,)), ("sent", "<u4", (4,)), ("hdr_bools", "<u4"), ("tokens", "<u4"), ("savings", "<i8", (4,))])
+
+
+class CuPicture(C.Structure):
+    _fields_ = [("d_tokens", C.c_void_p), ("d_n_tokens", C.c_void_p), ("d_counts", C.c_void_p), ("d_old_probs", C.c_void_p), ("d_eob_branch", C.c_void_p),
+                ("d_probs", C.c_void_p), ("d_hdr_bools", C.c_void_p), ("d_n_hdr_bools", C.c_void_p), ("d_segment", C.c_void_p), ("d_result", C.c_void_p),
+                ("n_tokens", C.c_uint32), ("max_tokens", C.c_uint32), ("n_prefix", C.c_uint16), ("n_suffix", C.c_uint16), ("prefix", C.c_uint16 * CU_PREFIX_MAX),
+                ("suffix", C.c_uint16 * CU_SUFFIX_MAX), ("pad_", C.c_uint32)]
+
+
+assert C.sizeof(CuPicture) == 528 and CU_RESULT_DTYPE.itemsize == 72
+
+
 # key-frame mode-info stage (svt_modes_tables / svt_modes_picture of include/svtvp9_hip.h)
 MODES_TABLES_DTYPE = np.dtype([("kf_y_mode_prob", "u1", (10, 10, 9)), ("kf_uv_mode_prob", "u1", (10, 9)), ("kf_partition_probs", "u1", (16, 3)), ("skip_probs", "u1", (3,))])
 assert MODES_TABLES_DTYPE.itemsize == 900 + 90 + 48 + 3
@@ -305,7 +321,10 @@ EXPORTS = [
     "svt_hip_vp9_scan_tables", "svt_hip_tokenize_blocks_device", "svt_hip_tokenize_blocks", "svt_hip_tokenize_blocks_host", "svt_hip_tokenize_batch_device", "svt_hip_tokenize_picture",
     "svt_hip_tokenize_capacity",
     "svt_hip_boolcode_set_tables", "svt_hip_boolcode_batch_device", "svt_hip_boolcode", "svt_hip_boolcode_host", "svt_hip_boolcode_capacity", "svt_hip_boolcode_bools_capacity",
-    "svt_hip_boolcode_geometry",
+    "svt_hip_boolcode_geometry", "svt_hip_boolcode_batch_tables_device",
+    "svt_hip_coef_update_batch_device", "svt_hip_coef_update_picture", "svt_hip_coef_update_bools_capacity", "svt_hip_coef_update_geometry",
+    "svt_hip_coef_update_cost_table", "svt_hip_coef_update_remap_tables",
+    "svt_hip_frame_header_parts_host", "svt_hip_frame_header_coef_host", "svt_hip_frame_read_header_coef_host",
     "svt_hip_modes_set_tables", "svt_hip_modes_kf_batch_device", "svt_hip_modes_kf_picture", "svt_hip_modes_segments", "svt_hip_modes_bools_capacity",
     "svt_hip_modes_inter_set_tables", "svt_hip_modes_inter_batch_device", "svt_hip_modes_inter_picture", "svt_hip_modes_inter_bools_capacity",
     "svt_hip_mvrefs_batch_device", "svt_hip_mvrefs_picture",
@@ -350,6 +369,17 @@ def load():
         _lib.svt_hip_boolcode_bools_capacity.restype = C.c_uint32
         _lib.svt_hip_boolcode_bools_capacity.argtypes = [C.c_uint32]
         _lib.svt_hip_boolcode_geometry.restype = None
+        _lib.svt_hip_boolcode_batch_tables_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        _lib.svt_hip_coef_update_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        _lib.svt_hip_coef_update_picture.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.svt_hip_coef_update_bools_capacity.restype = C.c_uint32
+        _lib.svt_hip_coef_update_geometry.restype = None
+        _lib.svt_hip_coef_update_cost_table.restype = C.POINTER(C.c_uint16)
+        _lib.svt_hip_coef_update_remap_tables.restype = None
+        _lib.svt_hip_coef_update_remap_tables.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.svt_hip_frame_header_parts_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
+        _lib.svt_hip_frame_header_coef_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.svt_hip_frame_read_header_coef_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.svt_hip_modes_segments.restype = C.c_uint32
         _lib.svt_hip_modes_bools_capacity.restype = C.c_uint32
         _lib.svt_hip_modes_inter_bools_capacity.restype = C.c_uint32

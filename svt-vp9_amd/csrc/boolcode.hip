@@ -167,22 +167,33 @@ __global__ __launch_bounds__(256) void svt_bc_tilescan_kernel(const bc_batch_dev
     }
 }
 
-__global__ __launch_bounds__(256) void svt_bc_expand_kernel(const bc_batch_dev *__restrict__ B, const svt_bool_tables *__restrict__ tables) {
-    __shared__ uint32_t s_w[4];
-    const bc_stream_dev &P = B->s[blockIdx.y];
-    const uint32_t       n_items = P.state[ST_ITEMS];
-    if (P.state[ST_OVER] || blockIdx.x * BC_ITEMS >= n_items) return;
-    bc_items it;
-    load_items(P, n_items, blockIdx.x * BC_ITEMS + threadIdx.x * 4, it);
-    uint32_t total;
-    uint32_t off = 1 + P.tile_sum[blockIdx.x] + block_excl_scan<uint32_t>((uint32_t)(it.cnt[0] + it.cnt[1] + it.cnt[2] + it.cnt[3]), s_w, &total);
-    _Pragma("unroll") for (int j = 0; j < 4; j++) {
-        if (!it.cnt[j]) continue;
-        if (it.raw[j]) P.bools[off] = (uint16_t)it.rec[j];
-        else (void)svt_bool_expand(it.rec[j], it.skip[j], tables, P.bools + off);
-        off += (uint32_t)it.cnt[j];
+/* The expand kernel's text, instantiated twice on "coefficient probabilities per stream".  The table's only reader.  A macro and not a
+ * template: through a templated device function the plain instance compiles to the code it always was but for three commuted adds, and
+ * svt_hip_boolcode_batch_device is to run the code object it ran before the second instance existed, instruction for instruction. */
+#define BC_EXPAND_BODY(EXPAND)                                                                                                                          \
+    __shared__ uint32_t s_w[4];                                                                                                                         \
+    const bc_stream_dev &P = B->s[blockIdx.y];                                                                                                          \
+    const uint32_t       n_items = P.state[ST_ITEMS];                                                                                                   \
+    if (P.state[ST_OVER] || blockIdx.x * BC_ITEMS >= n_items) return;                                                                                   \
+    bc_items it;                                                                                                                                        \
+    load_items(P, n_items, blockIdx.x * BC_ITEMS + threadIdx.x * 4, it);                                                                                \
+    uint32_t total;                                                                                                                                     \
+    uint32_t off = 1 + P.tile_sum[blockIdx.x] + block_excl_scan<uint32_t>((uint32_t)(it.cnt[0] + it.cnt[1] + it.cnt[2] + it.cnt[3]), s_w, &total);      \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                                                     \
+        if (!it.cnt[j]) continue;                                                                                                                       \
+        if (it.raw[j]) P.bools[off] = (uint16_t)it.rec[j];                                                                                              \
+        else (void)EXPAND;                                                                                                                              \
+        off += (uint32_t)it.cnt[j];                                                                                                                     \
     }
+__global__ __launch_bounds__(256) void svt_bc_expand_kernel(const bc_batch_dev *__restrict__ B, const svt_bool_tables *__restrict__ tables) {
+    BC_EXPAND_BODY(svt_bool_expand(it.rec[j], it.skip[j], tables, P.bools + off))
 }
+/* coef[stream] when it is set, the context's coefficient probabilities otherwise */
+__global__ __launch_bounds__(256) void svt_bc_expand_tables_kernel(const bc_batch_dev *__restrict__ B, const svt_bool_tables *__restrict__ tables,
+                                                                    const uint8_t *const *__restrict__ coef) {
+    BC_EXPAND_BODY(svt_bool_expand_probs(it.rec[j], it.skip[j], coef[blockIdx.y] ? coef[blockIdx.y] : tables->coef_probs, tables, P.bools + off))
+}
+#undef BC_EXPAND_BODY
 
 /* the j-th (0 .. 7) bool record of a 16-byte group */
 __device__ __forceinline__ uint32_t bool_of(const uint4 &q, int j) {
@@ -333,7 +344,8 @@ extern "C" int32_t svt_hip_boolcode_set_tables(svt_hip_ctx *ctx, const svt_bool_
     return svt_ctx_set_tables(ctx, SVT_SLOT_BC_TABLES, tables, sizeof(svt_bool_tables), "boolcode");
 }
 
-extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams) {
+/* both batch entries: d_coef_probs null = the context's table for every stream (the plain expand kernel, the descriptor alone is staged) */
+static int32_t bc_batch(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams, const uint8_t *const *d_coef_probs) {
     if (!ctx || !streams || n_streams < 1 || n_streams > SVT_BOOL_MAX_STREAMS) return svt_set_error(SVT_HIP_ERR_BAD_PARAMETER, "boolcode: bad argument");
     size_t   total = 0;
     uint32_t max_tiles = 1, max_chunks = 1, max_words = 1;
@@ -373,19 +385,26 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
         P.start = (uint32_t *)scratch; scratch += align16(sizeof(uint32_t) * (size_t)chunks * 2);
         P.acc = (unsigned long long *)scratch; scratch += align16(sizeof(unsigned long long) * (size_t)words);
     }
-    void *h = nullptr, *d = nullptr;
-    if (svt_ctx_stage(ctx, sizeof hb, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: descriptor buffers");
+    void        *h = nullptr, *d = nullptr;
+    const size_t staged = sizeof hb + (d_coef_probs ? sizeof(const uint8_t *) * SVT_BOOL_MAX_STREAMS : 0);
+    if (svt_ctx_stage(ctx, staged, &h, &d)) return svt_set_error(SVT_HIP_ERR_NO_RESOURCES, "boolcode: descriptor buffers");
     svt_ctx_timer timer(ctx);
     HIP_TRY(timer.begin());
     memcpy(h, &hb, sizeof hb);
-    HIP_TRY(svt_ctx_stage_send(ctx, sizeof hb));
+    if (d_coef_probs) {
+        const uint8_t **hc = (const uint8_t **)((uint8_t *)h + sizeof hb);
+        for (int i = 0; i < SVT_BOOL_MAX_STREAMS; i++) hc[i] = i < n_streams ? d_coef_probs[i] : nullptr;
+    }
+    HIP_TRY(svt_ctx_stage_send(ctx, staged));
     const bc_batch_dev    *dB = (const bc_batch_dev *)d;
     const svt_bool_tables *dT = (const svt_bool_tables *)ctx->slot[SVT_SLOT_BC_TABLES];
     const dim3             ns((unsigned)n_streams);
     hipLaunchKernelGGL(svt_bc_segscan_kernel, ns, dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_count_kernel, dim3(max_tiles, n_streams), dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_tilescan_kernel, ns, dim3(256), 0, ctx->stream, dB);
-    hipLaunchKernelGGL(svt_bc_expand_kernel, dim3(max_tiles, n_streams), dim3(256), 0, ctx->stream, dB, dT);
+    if (d_coef_probs)
+        hipLaunchKernelGGL(svt_bc_expand_tables_kernel, dim3(max_tiles, n_streams), dim3(256), 0, ctx->stream, dB, dT, (const uint8_t *const *)((const uint8_t *)d + sizeof hb));
+    else hipLaunchKernelGGL(svt_bc_expand_kernel, dim3(max_tiles, n_streams), dim3(256), 0, ctx->stream, dB, dT);
     hipLaunchKernelGGL(svt_bc_maps_kernel, dim3((max_chunks + 3) / 4, n_streams), dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_chain_kernel, ns, dim3(256), 0, ctx->stream, dB);
     hipLaunchKernelGGL(svt_bc_clear_kernel, dim3((max_words + 1023) / 1024, n_streams), dim3(256), 0, ctx->stream, dB);
@@ -393,6 +412,13 @@ extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_str
     hipLaunchKernelGGL(svt_bc_carry_kernel, ns, dim3(256), 0, ctx->stream, dB);
     HIP_TRY(timer.end());
     return SVT_HIP_OK;
+}
+
+extern "C" int32_t svt_hip_boolcode_batch_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams) {
+    return bc_batch(ctx, n_streams, streams, nullptr);
+}
+extern "C" int32_t svt_hip_boolcode_batch_tables_device(svt_hip_ctx *ctx, int32_t n_streams, const svt_bool_stream *streams, const uint8_t *const *d_coef_probs) {
+    return bc_batch(ctx, n_streams, streams, d_coef_probs);
 }
 
 extern "C" int32_t svt_hip_boolcode(svt_hip_ctx *ctx, const uint32_t *tokens, uint32_t n_tokens, const uint16_t *bools, uint32_t n_bools,

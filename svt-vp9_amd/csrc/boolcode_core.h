@@ -37,11 +37,12 @@ SVT_HD int svt_bool_count(int tok, int skip0) {
     return head + 2 + svt_bool_tree_len(tok) + svt_bool_cat_bits(tok) + 1;
 }
 
-/* writes svt_bool_count(token, skip0) records to out */
-SVT_HD int svt_bool_expand(uint32_t rec, int skip0, const svt_bool_tables *t, uint16_t *out) {
+/* writes svt_bool_count(token, skip0) records to out; coef_probs: the 576 x 3 coefficient probabilities of the stream (t's own, or
+ * another picture's: svt_hip_boolcode_batch_tables_device), pareto and cat_probs are t's */
+SVT_HD int svt_bool_expand_probs(uint32_t rec, int skip0, const uint8_t *coef_probs, const svt_bool_tables *t, uint16_t *out) {
     const int      tok = (int)SVT_TOK_TOKEN(rec);
     const uint32_t e = SVT_TOK_EXTRA(rec), row = SVT_TOK_PROB_ROW(rec) < 576 ? SVT_TOK_PROB_ROW(rec) : 575;
-    const uint8_t *p = t->coef_probs + 3 * row;
+    const uint8_t *p = coef_probs + 3 * row;
     int            n = 0;
     if (tok >= SVT_TOK_EOB) { out[0] = SVT_BOOL_RECORD(0, p[0]); return 1; }
     if (!skip0) out[n++] = SVT_BOOL_RECORD(1, p[0]);
@@ -66,6 +67,7 @@ SVT_HD int svt_bool_expand(uint32_t rec, int skip0, const svt_bool_tables *t, ui
     out[n++] = SVT_BOOL_RECORD(e & 1, 128);
     return n;
 }
+SVT_HD int svt_bool_expand(uint32_t rec, int skip0, const svt_bool_tables *t, uint16_t *out) { return svt_bool_expand_probs(rec, skip0, t->coef_probs, t, out); }
 
 /* one symbol from range r (128 .. 255): *split is what a 1 adds to the low end; returns next range | shift << 8 */
 SVT_HD uint32_t svt_bool_step(uint32_t r, uint32_t rec, uint32_t *split) {

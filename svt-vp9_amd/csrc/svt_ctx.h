@@ -30,6 +30,7 @@ enum svt_ctx_slot_id {
     SVT_SLOT_MII_SB_OFF, SVT_SLOT_MII_TABLES,                                                /* modeinfo_inter.hip: the same */
     SVT_SLOT_MVR_PART,                                                                       /* mvrefs.hip: per-SB partial sums */
     SVT_SLOT_MDI_PART, SVT_SLOT_MDI_LABEL,                                                   /* md_inter.hip: partial sums, the labelled records */
+    SVT_SLOT_CU_SCRATCH,                                                                     /* coef_update.hip: partial histograms, the sizes' sections */
     SVT_CTX_SLOTS
 };
 #define SVT_CTX_RING 64

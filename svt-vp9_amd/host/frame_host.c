@@ -6,6 +6,8 @@
  *     clears them), so update_coef_probs writes a 0 bit per transform size (:679-681) and every eb_vp9_cond_prob_diff_update
  *     (VPX/vp9_subexp.c:173-185), prob_diff_update (:56-66) and update_mv (VPX/vp9_encodemv.c:144-155) a 0 at probability 252 -- and is
  *     built as raw bool records and coded by svt_hip_boolcode_host: no second writer;
+ *   - svt_hip_frame_header_parts_host / svt_hip_frame_header_coef_host: the same records in front of and behind update_coef_probs, and the
+ *     two headers around a coefficient section that does update (csrc/coef_update.hip), from the same text;
  *   - svt_hip_frame_show_existing_host: the one-byte frame of show_existing_frame;
  *   - svt_hip_frame_assemble_host: the packet layout of csrc/frame_core.h over host pointers, the model of the assembly kernel.
  */
@@ -151,14 +153,16 @@ static uint32_t uncompressed_header(bit_writer *w, const svt_frame_params *p) {
     return at;
 }
 
-/* write_compressed_header (:1292-1367) as bool records; returns their number (<= SVT_FRAME_COMPRESSED_MAX_BOOLS) */
-static uint32_t compressed_bools(const svt_frame_params *p, uint16_t *b) {
+/* write_compressed_header (:1292-1367) as bool records, in two parts: what stands in front of update_coef_probs and what stands behind
+ * it; together with the section in between at most SVT_FRAME_COMPRESSED_MAX_BOOLS when the section is four "no update" bits */
+static void compressed_parts(const svt_frame_params *p, uint16_t *b, uint32_t *n_prefix, uint16_t *suffix, uint32_t *n_suffix) {
     uint32_t n = 0;
 #define LITERAL_BIT(bit) (b[n++] = SVT_BOOL_RECORD((bit), 128))
 #define NO_UPDATE(count) do { for (int k_ = 0; k_ < (count); k_++) b[n++] = SVT_BOOL_RECORD(0, 252); } while (0)
     LITERAL_BIT(1); LITERAL_BIT(1); /* encode_txfm_probs: min(tx_mode, ALLOW_32X32) = 3, */
     LITERAL_BIT(0);                 /* not TX_MODE_SELECT */
-    for (int t = 0; t < 4; t++) LITERAL_BIT(0); /* update_coef_probs: tx_totals <= 20 for TX_4X4 .. TX_32X32 */
+    *n_prefix = n;
+    b = suffix; n = 0;              /* update_coef_probs stands here */
     NO_UPDATE(3);                   /* update_skip_probs */
     if (p->frame_type != 0 && !p->intra_only) {
         NO_UPDATE(7 * 3);           /* inter_mode_probs */
@@ -182,30 +186,58 @@ static uint32_t compressed_bools(const svt_frame_params *p, uint16_t *b) {
     }
 #undef LITERAL_BIT
 #undef NO_UPDATE
-    return n;
+    *n_suffix = n;
 }
 
-int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes, uint32_t *compressed_bytes) {
+int32_t svt_hip_frame_header_parts_host(const svt_frame_params *p, uint16_t *prefix, uint32_t *n_prefix, uint16_t *suffix, uint32_t *n_suffix) {
+    if (!p || !prefix || !n_prefix || !suffix || !n_suffix || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
+    compressed_parts(p, prefix, n_prefix, suffix, n_suffix);
+    return SVT_HIP_OK;
+}
+
+/* the uncompressed header, then the compressed header coded from the given records, first_part_size from the coder's answer */
+static int32_t header_from_bools(const svt_frame_params *p, const uint16_t *bools, uint32_t n, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes,
+                                 uint32_t *compressed_bytes) {
     static const svt_bool_tables no_tables; /* the stream has no token records: never read */
-    if (!p || !out || !uncompressed_bytes || !compressed_bytes || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
     bit_writer w;
     memset(&w, 0, sizeof w);
     const uint32_t at = uncompressed_header(&w, p), ub = (w.bits + 7) >> 3;
-    uint16_t       bools[SVT_FRAME_COMPRESSED_MAX_BOOLS];
-    const uint32_t n = compressed_bools(p, bools);
+    if (ub > capacity) return SVT_HIP_ERR_BAD_PARAMETER;
     const svt_bool_segment seg = {0, n, 1};
-    uint8_t        comp[SVT_FRAME_COMPRESSED_MAX];
-    uint32_t       cb = 0;
-    const int32_t  rc = svt_hip_boolcode_host(&no_tables, NULL, 0, bools, n, &seg, 1, comp, sizeof comp, &cb);
+    uint32_t               cb = 0;
+    const int32_t          rc = svt_hip_boolcode_host(&no_tables, NULL, 0, bools, n, &seg, 1, out + ub, capacity - ub, &cb);
     if (rc) return rc;
-    if (cb > sizeof comp || ub + cb > capacity) return SVT_HIP_ERR_BAD_PARAMETER;
+    if (cb > 0xffff || cb > capacity - ub) return SVT_HIP_ERR_BAD_PARAMETER;
     for (int i = 0; i < 16; i++) /* first_part_size over its place holder */
         if ((cb >> (15 - i)) & 1u) w.buf[(at + i) >> 3] |= (uint8_t)(0x80u >> ((at + i) & 7));
     memcpy(out, w.buf, ub);
-    memcpy(out + ub, comp, cb);
     *uncompressed_bytes = ub;
     *compressed_bytes = cb;
     return SVT_HIP_OK;
+}
+
+int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *uncompressed_bytes, uint32_t *compressed_bytes) {
+    if (!p || !out || !uncompressed_bytes || !compressed_bytes || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
+    uint16_t bools[SVT_FRAME_COMPRESSED_MAX_BOOLS], suffix[SVT_FRAME_COMPRESSED_MAX_BOOLS];
+    uint32_t n = 0, ns = 0;
+    compressed_parts(p, bools, &n, suffix, &ns);
+    for (int t = 0; t < 4; t++) bools[n++] = SVT_BOOL_RECORD(0, 128); /* update_coef_probs: tx_totals <= 20 for TX_4X4 .. TX_32X32 */
+    memcpy(bools + n, suffix, sizeof(uint16_t) * ns);
+    uint8_t  hdr[SVT_FRAME_HEADER_MAX + 8];
+    uint32_t ub = 0, cb = 0;
+    const int32_t rc = header_from_bools(p, bools, n + ns, hdr, sizeof hdr, &ub, &cb);
+    if (rc) return rc;
+    if (cb > SVT_FRAME_COMPRESSED_MAX || ub + cb > capacity) return SVT_HIP_ERR_BAD_PARAMETER;
+    memcpy(out, hdr, ub + cb);
+    *uncompressed_bytes = ub;
+    *compressed_bytes = cb;
+    return SVT_HIP_OK;
+}
+
+int32_t svt_hip_frame_header_coef_host(const svt_frame_params *p, const uint16_t *hdr_bools, uint32_t n_hdr_bools, uint8_t *out, uint32_t capacity,
+                                       uint32_t *uncompressed_bytes, uint32_t *compressed_bytes) {
+    if (!p || !hdr_bools || !out || !uncompressed_bytes || !compressed_bytes || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
+    return header_from_bools(p, hdr_bools, n_hdr_bools, out, capacity, uncompressed_bytes, compressed_bytes);
 }
 
 int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out) {

@@ -5,11 +5,12 @@
  * read_compressed_header of the VP9 specification (6.2, 6.3; libvpx vp9_decodeframe.c), not the writer run backwards: where the decoder
  * infers a value instead of reading it (compound prediction allowed from the sign biases, lossless from the quantiser fields, the flags
  * under error_resilient_mode) so does this reader, and a stream whose writer assumed otherwise does not parse back to its parameters.
- * The field order is host/frame_host.c's uncompressed_header / compressed_bools, read instead of written; the bool decoder is
- * csrc/read_core.h's.  The compressed header is decoded bool by bool; a set update flag returns SVT_HIP_ERR_UNSUPPORTED (the writers
- * never send a forward update, include/svtvp9_hip.h: the no-update rule).
+ * The field order is host/frame_host.c's uncompressed_header / compressed_parts, read instead of written; the bool decoder is
+ * csrc/read_core.h's.  The compressed header is decoded bool by bool; a set update flag returns SVT_HIP_ERR_UNSUPPORTED (the plain
+ * writers never send a forward update, include/svtvp9_hip.h: the no-update rule) -- except that svt_hip_frame_read_header_coef_host reads
+ * coefficient-probability updates (the writer is csrc/coef_update.hip's stage) into the caller's table, with the writer's own entry order.
  *
- * Memory safety: no byte at or beyond frame + size is read (both readers are bounded), nothing but *info is written, every loop has a
+ * Memory safety: no byte at or beyond frame + size is read (both readers are bounded), nothing but *info (and the coefficient probabilities of the coef reader's table) is written, every loop has a
  * constant trip count.
  */
 #include <stdio.h>
@@ -17,6 +18,7 @@
 #include "../../include/svtvp9_hip.h"
 #include "../csrc/frame_core.h"
 #include "../csrc/read_core.h"
+#include "../csrc/coef_update_core.h"
 
 int32_t svt_set_error_c(int32_t code, const char *msg); /* csrc/api.hip: the message behind svt_hip_last_error */
 
@@ -54,8 +56,26 @@ static int any_update(svt_bool_reader *b, int count) {
     return set;
 }
 
-int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
-                                       svt_frame_read_info *info) {
+/* the inverse of encode_term_subexp / encode_uniform (VPX/vp9_subexp.c:76-102) */
+static int read_term_subexp(svt_bool_reader *b) {
+    if (!svt_bool_read(b, 128)) return (int)svt_bool_literal(b, 4);
+    if (!svt_bool_read(b, 128)) return (int)svt_bool_literal(b, 4) + 16;
+    if (!svt_bool_read(b, 128)) return (int)svt_bool_literal(b, 5) + 32;
+    const int v = (int)svt_bool_literal(b, 7), m = (1 << 8) - 191;
+    return 64 + (v < m ? v : (v << 1) - m + svt_bool_read(b, 128));
+}
+/* read_coef_probs of one transform size that is updated: the writer's entries in the writer's order (csrc/coef_update_core.h) */
+static void read_coef_updates(svt_bool_reader *b, uint8_t *probs432) {
+    for (int e = 0; e < SVT_CU_ENTRIES; e++) {
+        int       node;
+        const int at = 3 * svt_cu_entry(e, &node) + node;
+        if (svt_bool_read(b, SVT_CU_UPD_PROB)) probs432[at] = (uint8_t)svt_cu_inv_remap(read_term_subexp(b), probs432[at]);
+    }
+}
+
+/* both header readers: tables null = a coefficient update is refused, as every other update is */
+static int32_t read_header(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], svt_frame_read_info *info,
+                           svt_bool_tables *tables) {
     if (!frame || !info || !last_ref_deltas || !last_mode_deltas) return fail(SVT_HIP_ERR_BAD_PARAMETER, "null argument");
     memset(info, 0, sizeof *info);
     if (size == 0) return fail(SVT_HIP_ERR_BAD_PARAMETER, "empty frame");
@@ -157,7 +177,10 @@ int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, cons
     if (info->tx_mode == 3) info->tx_mode = (uint8_t)(3 + svt_bool_read(&b, 128));
     if (info->tx_mode == 4) return fail(SVT_HIP_ERR_UNSUPPORTED, "TX_MODE_SELECT");
     for (int t = 0; t <= info->tx_mode; t++) /* read_coef_probs: one update bit per transform size up to the mode's largest */
-        if (svt_bool_read(&b, 128)) return fail(SVT_HIP_ERR_UNSUPPORTED, "coefficient probability update");
+        if (svt_bool_read(&b, 128)) {
+            if (!tables) return fail(SVT_HIP_ERR_UNSUPPORTED, "coefficient probability update");
+            read_coef_updates(&b, tables->coef_probs + 432 * t);
+        }
     int upd = any_update(&b, 3); /* skip */
     p->reference_mode = SVT_MODES_SINGLE_REFERENCE;
     if (p->frame_type != 0 && !p->intra_only && !upd) {
@@ -180,6 +203,16 @@ int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, cons
     if (upd) return fail(SVT_HIP_ERR_UNSUPPORTED, "forward probability update");
     if (svt_bool_past_end(&b)) return fail(SVT_HIP_ERR_BAD_PARAMETER, "the compressed header ends inside a symbol");
     return SVT_HIP_OK;
+}
+
+int32_t svt_hip_frame_read_header_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
+                                       svt_frame_read_info *info) {
+    return read_header(frame, size, last_ref_deltas, last_mode_deltas, info, NULL);
+}
+int32_t svt_hip_frame_read_header_coef_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2],
+                                            svt_frame_read_info *info, svt_bool_tables *tables_inout) {
+    if (!tables_inout) return fail(SVT_HIP_ERR_BAD_PARAMETER, "null argument");
+    return read_header(frame, size, last_ref_deltas, last_mode_deltas, info, tables_inout);
 }
 
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
