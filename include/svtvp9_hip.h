@@ -1621,6 +1621,12 @@ int32_t svt_hip_frame_header_host(const svt_frame_params *p, uint8_t *out, uint3
 int32_t svt_hip_frame_header_parts_host(const svt_frame_params *p, uint16_t *prefix, uint32_t *n_prefix, uint16_t *suffix, uint32_t *n_suffix);
 int32_t svt_hip_frame_header_coef_host(const svt_frame_params *p, const uint16_t *hdr_bools, uint32_t n_hdr_bools, uint8_t *out, uint32_t capacity,
                                        uint32_t *uncompressed_bytes, uint32_t *compressed_bytes);
+/* The uncompressed header alone, from the text svt_hip_frame_header_host writes it with: *bytes of it (at most
+ * SVT_FRAME_UNCOMPRESSED_MAX), the 16 bits of first_part_size left 0, *size_bit their bit position (bit 0 = the most significant bit of
+ * out[0]).  For callers whose compressed header is coded on the device (svt_hip_frame_parts_batch_device fills the field in).
+ * Refused as above. */
+#define SVT_FRAME_UNCOMPRESSED_MAX 27
+int32_t svt_hip_frame_header_uncompressed_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *bytes, uint32_t *size_bit);
 /* the one-byte frame that shows DPB slot dpb_slot (0 .. 7): eb_vp9_pack_bitstream with show_existing_frame set */
 int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out);
 
@@ -1718,6 +1724,15 @@ int32_t svt_hip_frame_read_host(const uint8_t *frame, uint32_t size, const int8_
                                 int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables,
                                 const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info, svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi,
                                 svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result);
+/* header and tile in one call for frames whose compressed header updates coefficient probabilities (the entropy pass's coefficient-update
+ * mode): svt_hip_frame_read_header_coef_host on a COPY of bool_tables -- the table the update was coded against -- then
+ * svt_hip_tile_read_host under the copy.  tables_out (may be NULL) receives the copy, the table the tile was coded with; the caller's
+ * tables are not written.  The reader above keeps refusing a coefficient update. */
+int32_t svt_hip_frame_read_coef_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
+                                     int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables,
+                                     const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info,
+                                     svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi, svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map,
+                                     svt_tile_read_result *result, svt_bool_tables *tables_out);
 
 /* one picture of a batch.  header / trailer are HOST bytes (the two headers; up to four show-existing bytes): they travel to the device
  * inside the descriptor upload of the call.  d_tile / d_tile_size are the bool coder's d_bytes / d_size; d_tile may have ANY alignment. */
@@ -1751,6 +1766,35 @@ int32_t svt_hip_frame_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_f
 int32_t svt_hip_frame_assemble_host(int32_t n_pics, const svt_frame_packet *packets, uint8_t *arena, uint32_t arena_capacity, svt_frame_entry *table);
 /* the assembly kernel's constants: workgroups per picture and bytes they move in one pass of the grid-stride loop */
 void svt_hip_frame_geometry(int32_t *workgroups_per_picture, int32_t *bytes_per_pass);
+
+/* The same assembly for a picture whose compressed header is coded on the device too (a header with coefficient-probability updates,
+ * svt_hip_coef_update_batch_device): packet i = uncompressed header || compressed[0 .. *d_compressed_size) || tile[0 .. *d_tile_size) ||
+ * trailer.  header holds the HOST bytes of the uncompressed header (svt_hip_frame_header_uncompressed_host); its bits
+ * [size_bit, size_bit + 16) are first_part_size and leave as *d_compressed_size, most significant bit first, whatever the host put there
+ * (replaced, not OR-ed into).  d_compressed / d_compressed_size / compressed_capacity and d_tile / d_tile_size / tile_capacity are the
+ * bool coder's d_bytes / d_size / capacity of the two streams; both buffers may have ANY alignment. */
+typedef struct svt_frame_parts_packet {
+    const uint8_t  *d_compressed;
+    const uint32_t *d_compressed_size;
+    const uint8_t  *d_tile;
+    const uint32_t *d_tile_size;
+    uint32_t        compressed_capacity, tile_capacity; /* as handed to the bool coder */
+    uint16_t        size_bit;           /* size_bit + 16 <= 8 * header_len */
+    uint8_t         header_len;         /* <= SVT_FRAME_UNCOMPRESSED_MAX */
+    uint8_t         trailer_len;        /* <= 4 */
+    uint8_t         header[SVT_FRAME_UNCOMPRESSED_MAX], trailer[4];
+    uint8_t         pad_[5];
+} svt_frame_parts_packet;               /* 80 bytes */
+/* Table, offsets, density, d_table[n_pics], the saturation of sums and the arena-capacity contract are svt_hip_frame_batch_device's.  A
+ * picture gets SVT_FRAME_SIZE_NONE when its tile size is SVT_BOOL_SIZE_OVERFLOW or above tile_capacity, or when its compressed size is
+ * SVT_BOOL_SIZE_OVERFLOW, 0, above compressed_capacity or above 0xFFFF (what first_part_size can say).  Asynchronous on the context's
+ * stream, one descriptor upload, one launch, no read-modify-write of the arena.  Refused, nothing launched: n_pics outside
+ * 1 .. SVT_FRAME_MAX_PICS, a null pointer (d_arena may be null when arena_capacity is 0, d_tile / d_compressed when their capacity is
+ * 0), header_len above SVT_FRAME_UNCOMPRESSED_MAX, size_bit + 16 beyond the header's bits, trailer_len above 4. */
+int32_t svt_hip_frame_parts_batch_device(svt_hip_ctx *ctx, int32_t n_pics, const svt_frame_parts_packet *packets, uint8_t *d_arena, uint32_t arena_capacity,
+                                         svt_frame_entry *d_table);
+/* host form of the same text (csrc/frame_core.h), pure CPU; every pointer a host pointer */
+int32_t svt_hip_frame_assemble_parts_host(int32_t n_pics, const svt_frame_parts_packet *packets, uint8_t *arena, uint32_t arena_capacity, svt_frame_entry *table);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* IVF container (host only): what the reference's sample application wraps the encoder's packets in   */
@@ -1850,6 +1894,7 @@ int32_t svt_hip_entropy_batch_device(svt_hip_ctx *ctx, svt_entropy_work *work, i
 #define SVT_ENT_STAGE_RESULT 6
 #define SVT_ENT_STAGE_FRAME 7
 #define SVT_ENT_STAGE_END 8
+#define SVT_ENT_STAGE_COEF_UPDATE 9 /* between MODES and GATE, in the coefficient-update mode only (below) */
 void svt_hip_entropy_work_set_stage_hook(svt_entropy_work *work, void (*hook)(void *user, int32_t stage), void *user);
 /* where picture `pic` (0 .. max_pics - 1) of the workspace keeps its intermediates: for inspection and measurement */
 typedef struct svt_entropy_buffers {
@@ -1865,6 +1910,41 @@ typedef struct svt_entropy_buffers {
 } svt_entropy_buffers;
 int32_t svt_hip_entropy_work_buffers(const svt_entropy_work *work, int32_t pic, svt_entropy_buffers *out);
 
+/* Forward coefficient-probability updates, an opt-in mode of the pass.  With it on a batch goes from grids, coefficients and eob maps to
+ * dense packets whose compressed headers carry the coefficient updates (svt_hip_coef_update_batch_device) and whose tiles are coded under
+ * the updated probabilities, on one stream, no host round trip.  The order is then: headers (host: the uncompressed header and
+ * svt_hip_frame_header_parts_host) -> tokeniser (with counts) -> labelling -> mode info -> coefficient update (d_n_tokens the tokeniser's
+ * total on the device, max_tokens the limits', d_old_probs NULL) -> gate -> bool coder over the tiles under every picture's own table
+ * (svt_hip_boolcode_batch_tables_device) -> bool coder over the compressed headers (a second call: 32 pictures make 64 streams, above
+ * SVT_BOOL_MAX_STREAMS; one path for every batch size) -> result -> svt_hip_frame_parts_batch_device.  The stage hook reports
+ * SVT_ENT_STAGE_COEF_UPDATE between MODES and GATE in this mode only.  With the mode off the pass is what it was.
+ * Every picture is coded against the context's table: the pass refuses, with nothing launched, a picture with !error_resilient_mode &&
+ * refresh_frame_context in this mode -- a decoder would keep the updated probabilities in its frame context while the next picture is
+ * again coded against the defaults.  Chaining pictures is out of scope.
+ * A picture the gate withholds (TOKENS_OVER ...) is safe: the update stage's scan is bounded by max_tokens, its header stream is coded and
+ * ignored.  The header stream itself cannot overflow (csrc/entropy_core.h), so the result record has no flag for it.
+ * svt_hip_entropy_work_set_coef_update: the first enabling allocates a second slab of svt_hip_entropy_coef_update_bytes(limits) bytes
+ * (SVT_HIP_ERR_NO_RESOURCES when that fails; the mode then stays off); later calls only switch.  It synchronises nothing: the switch
+ * holds for the calls enqueued after it.  Per picture the second slab holds, each part rounded up to 16: 4 * SVT_TOK_COUNTS coefficient
+ * counts (used when the picture's d_counts is NULL) + 2 304 eob_branch + 1 728 probabilities + 2 * svt_hip_coef_update_bools_capacity()
+ * header records + svt_hip_boolcode_capacity(svt_hip_coef_update_bools_capacity()) header bytes + sizeof(svt_cu_result) + 64 (the record
+ * count, the segment, the header's size); times max_pics.  0 for limits a workspace cannot be created under. */
+int32_t  svt_hip_entropy_work_set_coef_update(svt_hip_ctx *ctx, svt_entropy_work *work, int32_t on);
+uint64_t svt_hip_entropy_coef_update_bytes(const svt_entropy_limits *limits);
+typedef struct svt_entropy_coef_buffers {
+    uint32_t         *d_counts, *d_eob_branch;
+    uint8_t          *d_probs;
+    uint16_t         *d_hdr_bools;
+    uint8_t          *d_hdr_bytes;
+    svt_cu_result    *d_result;
+    uint32_t         *d_n_hdr_bools;
+    svt_bool_segment *d_segment;
+    uint32_t         *d_hdr_size;
+    uint32_t          hdr_bools_capacity, hdr_capacity;
+} svt_entropy_coef_buffers;
+/* refused while the mode has never been enabled on the workspace */
+int32_t svt_hip_entropy_work_coef_buffers(const svt_entropy_work *work, int32_t pic, svt_entropy_coef_buffers *out);
+
 /* The same pass on host pointers, one picture (host/entropy_host.c): the stages' host forms in the same order and the same gate text; the
  * model of the device entry.  packet (capacity bytes) receives header || tile || trailer; *packet_size its size, SVT_FRAME_SIZE_NONE for a
  * picture without a packet (nothing is then written).  limits->max_pics is not read.  detail (may be NULL) reports what only the host
@@ -1878,6 +1958,13 @@ typedef struct svt_entropy_host_detail {
 int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
                                 const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
                                 uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail);
+/* The pass in the coefficient-update mode on host pointers: the arguments of svt_hip_entropy_picture, the stages' host forms in the
+ * device entry's order of that mode and the same gate text; packet receives uncompressed header || compressed header || tile || trailer.
+ * probs (1 728 bytes, may be NULL) receives the probabilities the tile was coded with, update (may be NULL) the stage's record.  Refused
+ * as svt_hip_entropy_picture refuses, and a picture with !error_resilient_mode && refresh_frame_context */
+int32_t svt_hip_entropy_picture_coef(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
+                                     const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
+                                     uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail, uint8_t *probs, svt_cu_result *update);
 /* the gate's two rules and the result record on plain values (csrc/entropy_core.h): status NULL for an intra-only picture.  Returns what
  * the tile's size word becomes */
 uint32_t svt_hip_entropy_gate_host(uint32_t tok_total, uint32_t max_tokens, uint32_t n_bools, uint32_t bools_capacity, const uint32_t *status, uint32_t size,

@@ -262,6 +262,16 @@ class FramePacket(C.Structure):
 
 
 assert C.sizeof(FrameParams) == 64 and C.sizeof(FramePacket) == 88 and FRAME_ENTRY_DTYPE.itemsize == 8
+FRAME_UNCOMPRESSED_MAX = 27
+
+
+class FramePartsPacket(C.Structure):  # svt_frame_parts_packet: a packet whose compressed header is a device stream too
+    _fields_ = [("d_compressed", C.c_void_p), ("d_compressed_size", C.c_void_p), ("d_tile", C.c_void_p), ("d_tile_size", C.c_void_p),
+                ("compressed_capacity", C.c_uint32), ("tile_capacity", C.c_uint32), ("size_bit", C.c_uint16), ("header_len", C.c_uint8), ("trailer_len", C.c_uint8),
+                ("header", C.c_uint8 * FRAME_UNCOMPRESSED_MAX), ("trailer", C.c_uint8 * 4), ("pad_", C.c_uint8 * 5)]
+
+
+assert C.sizeof(FramePartsPacket) == 80
 
 
 # svt_frame_read_info: what svt_hip_frame_read_header_host returns
@@ -334,6 +344,9 @@ EXPORTS = [
     "svt_hip_entropy_limits_worst", "svt_hip_entropy_work_bytes", "svt_hip_entropy_work_create", "svt_hip_entropy_work_destroy", "svt_hip_entropy_batch_device",
     "svt_hip_entropy_work_set_stage_hook", "svt_hip_entropy_work_buffers", "svt_hip_entropy_picture", "svt_hip_entropy_gate_host", "svt_hip_entropy_deliverable",
     "svt_hip_compound_refs_from_sign_bias",
+    "svt_hip_frame_header_uncompressed_host", "svt_hip_frame_parts_batch_device", "svt_hip_frame_assemble_parts_host",
+    "svt_hip_entropy_work_set_coef_update", "svt_hip_entropy_coef_update_bytes", "svt_hip_entropy_work_coef_buffers", "svt_hip_entropy_picture_coef",
+    "svt_hip_frame_read_coef_host",
 ]
 
 _lib = None
@@ -391,6 +404,10 @@ def load():
         _lib.svt_hip_frame_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
         _lib.svt_hip_frame_assemble_host.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
         _lib.svt_hip_frame_geometry.restype = None
+        # (params, out, capacity, bytes, size_bit)
+        _lib.svt_hip_frame_header_uncompressed_host.argtypes = [C.c_void_p, C.c_void_p, _u32, C.POINTER(_u32), C.POINTER(_u32)]
+        _lib.svt_hip_frame_parts_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
+        _lib.svt_hip_frame_assemble_parts_host.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.c_void_p]
         _lib.svt_hip_encdec_work_destroy.restype = None
         _lib.svt_hip_host_free.restype = None
         _lib.svt_hip_encdec_work_set_stage_hook.restype = None
@@ -399,6 +416,7 @@ def load():
         _lib.svt_hip_tile_read_host.argtypes = [C.c_void_p, _u32] + [C.c_void_p] * 10
         _lib.svt_hip_frame_read_host.argtypes = [C.c_void_p, _u32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 11
         _lib.svt_hip_frame_read_header_host.argtypes = [C.c_void_p, _u32, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.svt_hip_frame_read_coef_host.argtypes = _lib.svt_hip_frame_read_host.argtypes + [C.c_void_p]      # (... , tables_out)
         # (ctx, d_pred, d_recon, d_blocks, size_count[4], d_qtabs, d_qcoeff, d_eob, d_overflow)
         _lib.svt_hip_recon_batch_device.argtypes = [C.c_void_p] * 9
         # (ctx, work, n_pics, pics, width, height, mi_stride, q_index, thr, pad_x, pad_y, d_status)
@@ -425,6 +443,12 @@ def load():
         _lib.svt_hip_entropy_work_set_stage_hook.restype = None
         _lib.svt_hip_entropy_work_set_stage_hook.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.svt_hip_entropy_work_buffers.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        # the coefficient-update mode: (ctx, work, on); (limits); (work, pic, out); svt_hip_entropy_picture's arguments + (probs, update)
+        _lib.svt_hip_entropy_work_set_coef_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        _lib.svt_hip_entropy_coef_update_bytes.restype = C.c_uint64
+        _lib.svt_hip_entropy_coef_update_bytes.argtypes = [C.c_void_p]
+        _lib.svt_hip_entropy_work_coef_buffers.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        _lib.svt_hip_entropy_picture_coef.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.POINTER(_u32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # (bool tables, modes tables, inter tables, pic, mi_stride, limits, packet, packet_capacity, packet_size, result, detail)
         _lib.svt_hip_entropy_picture.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, _u32, C.POINTER(_u32), C.c_void_p, C.c_void_p]
         # (tok_total, max_tokens, n_bools, bools_capacity, status, size, max_tile_bytes, verdict_a, result)
@@ -511,4 +535,11 @@ assert C.sizeof(EntropyPicture) == 112 and ENTROPY_RESULT_DTYPE.itemsize == 32 a
 ENT_BAD_GRID, ENT_TOKENS_OVER, ENT_MODE_BOOLS_OVER, ENT_UNFAITHFUL_MV, ENT_STREAM_OVER, ENT_TILE_OVER = 1, 2, 4, 8, 16, 32
 ENT_NEEDS_BACKWARD_ADAPTATION, ENT_LOSSLESS, ENT_COMP_FLAG_MISMATCH, ENT_REFERENCE_MODE_UNREAD = 1, 2, 4, 8
 ENT_STAGES = ("headers", "tokens", "labels", "modes", "gate", "boolcode", "result", "frame", "end")
+ENT_STAGE_COEF_UPDATE = 9  # reported between "modes" and "gate", in the coefficient-update mode only
+ENT_STAGES_COEF = ENT_STAGES + ("coef_update",)
+
+
+class EntropyCoefBuffers(C.Structure):  # svt_entropy_coef_buffers: a picture's part of the coefficient-update mode's slab
+    _fields_ = [(n, C.c_void_p) for n in ("d_counts", "d_eob_branch", "d_probs", "d_hdr_bools", "d_hdr_bytes", "d_result", "d_n_hdr_bools", "d_segment", "d_hdr_size")] + \
+               [("hdr_bools_capacity", C.c_uint32), ("hdr_capacity", C.c_uint32)]
 ENTROPY_STAGE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)

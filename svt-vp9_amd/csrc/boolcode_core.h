@@ -18,6 +18,8 @@
 #include "tokenize_core.h"
 
 #define SVT_BOOL_FRAME_TAIL 32 /* eb_vp9_stop_encode's (128, 0) bools; eb_vp9_start_encode adds one in front */
+/* bytes n bools occupy at most: 7 bits a bool, the framing bools, the marker byte (svt_hip_boolcode_capacity; n of a type wide enough) */
+#define SVT_BOOL_CAPACITY_OF(n) ((7 * ((n) + 1 + SVT_BOOL_FRAME_TAIL) + 7) / 8 + 2)
 /* eb_vp9_coef_con_tree (VPX/vp9_entropy.c), inner links only, one nibble per entry: {2, 6, -, 4, -, -, 8, 10, -, -, 12, 14, -, -, -, -} */
 #define SVT_BOOL_CON_TREE 0x0000EC00A8004062ull
 

@@ -53,6 +53,33 @@ SVT_HD int svt_ent_layout_of(int width, int height, int mi_stride, uint32_t max_
     return 0;
 }
 
+/* The second slab of a workspace, taken when the coefficient-update mode is first enabled: per picture what the update stage
+ * (csrc/coef_update.hip) reads and writes and the compressed header's stream.  The header stream cannot overflow: it holds at most
+ * SVT_ENT_HDR_BOOLS records whatever the picture, its buffer is the bool coder's capacity for that many, and that capacity is a
+ * first_part_size 16 bits can say -- so a picture's header never withholds it and the result record needs no flag for it. */
+#define SVT_ENT_HDR_BOOLS (SVT_CU_PREFIX_MAX + SVT_CU_SECTION_MAX + SVT_CU_SUFFIX_MAX)              /* svt_hip_coef_update_bools_capacity */
+#define SVT_ENT_HDR_BYTES SVT_BOOL_CAPACITY_OF(SVT_ENT_HDR_BOOLS)                                    /* svt_hip_boolcode_capacity of it: the same macro */
+#if SVT_ENT_HDR_BYTES > 0xFFFF
+#error "a compressed header with coefficient updates may exceed first_part_size"
+#endif
+typedef struct svt_ent_coef_layout {
+    uint64_t counts, eob_branch, probs, hdr_bools, hdr_bytes, result, words, bytes; /* byte offsets, multiples of 16; bytes: a picture's part */
+} svt_ent_coef_layout;
+/* the dwords of its `words`: the header's record count, its one segment {first, count, kind}, the coded header's size */
+enum { SVT_ENT_CW_N_HDR_BOOLS = 0, SVT_ENT_CW_SEGMENT = 1, SVT_ENT_CW_HDR_SIZE = 4, SVT_ENT_CW_WORDS = 16 };
+
+SVT_HD void svt_ent_coef_layout_of(svt_ent_coef_layout *l) {
+    uint64_t at = 0;
+    l->counts = at;     at += svt_ent_align16(4 * (uint64_t)SVT_TOK_COUNTS);
+    l->eob_branch = at; at += svt_ent_align16(4 * (uint64_t)SVT_CU_ROWS);
+    l->probs = at;      at += svt_ent_align16(SVT_CU_PROBS);
+    l->hdr_bools = at;  at += svt_ent_align16(2 * (uint64_t)SVT_ENT_HDR_BOOLS);
+    l->hdr_bytes = at;  at += svt_ent_align16(SVT_ENT_HDR_BYTES);
+    l->result = at;     at += svt_ent_align16(sizeof(svt_cu_result));
+    l->words = at;      at += 4 * SVT_ENT_CW_WORDS;
+    l->bytes = at;
+}
+
 /* the bool coder's own rule for a stream it takes: bit positions are 32-bit */
 SVT_HD int svt_ent_bools_codable(uint32_t max_bools) { return 7ull * ((uint64_t)max_bools + 1 + SVT_BOOL_FRAME_TAIL) < 0x100000000ull; }
 

@@ -5,6 +5,8 @@
  *   svt_frame_packet_size   bytes of a picture's packet, or SVT_FRAME_SIZE_NONE when its tile was not coded
  *   svt_frame_layout        offset of a picture from the sizes in front of it; the total and the pictures without a packet
  *   svt_frame_span          the part [0, n) of a run of bytes at arena position `pos` that lies below the arena's capacity
+ *   svt_frame_parts_size    svt_frame_packet_size for a packet whose compressed header is a device stream of its own
+ *   svt_frame_size_field_byte   a byte of the uncompressed header with first_part_size filled in
  *
  * SVT_FRAME_HEADER_MAX (include/svtvp9_hip.h) = 27 + 29 = 56, from the syntax (VPX/vp9_bitstream.c):
  *
@@ -40,8 +42,7 @@
 #include <stdint.h>
 #include "boolcode_core.h"
 
-#define SVT_FRAME_UNCOMPRESSED_MAX 27
-#define SVT_FRAME_COMPRESSED_MAX_BOOLS 210
+#define SVT_FRAME_COMPRESSED_MAX_BOOLS 210 /* (SVT_FRAME_UNCOMPRESSED_MAX = 27 stands in include/svtvp9_hip.h: a descriptor holds that header) */
 #define SVT_FRAME_COMPRESSED_MAX ((SVT_FRAME_COMPRESSED_MAX_BOOLS + 1 + SVT_BOOL_FRAME_TAIL - 16) / 8 + 1)
 #if SVT_FRAME_UNCOMPRESSED_MAX + SVT_FRAME_COMPRESSED_MAX != SVT_FRAME_HEADER_MAX
 #error "SVT_FRAME_HEADER_MAX does not follow from the syntax"
@@ -71,6 +72,27 @@ SVT_HD uint32_t svt_frame_layout(const uint32_t *sizes, int pic, uint32_t *none)
 SVT_HD uint32_t svt_frame_span(uint64_t pos, uint32_t n, uint32_t arena_capacity) {
     if (pos >= arena_capacity) return 0;
     return arena_capacity - pos < n ? (uint32_t)(arena_capacity - pos) : n;
+}
+
+/* A packet of three parts (svt_frame_parts_packet): compressed_size is what the bool coder left in the header stream's *d_size.  It
+ * must be a first_part_size a decoder accepts and the 16 bits can say: 1 .. 0xFFFF */
+SVT_HD uint32_t svt_frame_parts_size(uint32_t header_len, uint32_t trailer_len, uint32_t compressed_size, uint32_t compressed_capacity, uint32_t tile_size,
+                                     uint32_t tile_capacity) {
+    if (tile_size == SVT_BOOL_SIZE_OVERFLOW || tile_size > tile_capacity) return SVT_FRAME_SIZE_NONE;
+    if (compressed_size == SVT_BOOL_SIZE_OVERFLOW || compressed_size == 0 || compressed_size > compressed_capacity || compressed_size > 0xFFFFu) return SVT_FRAME_SIZE_NONE;
+    const uint64_t n = (uint64_t)header_len + compressed_size + tile_size + trailer_len;
+    return n >= SVT_FRAME_SIZE_NONE ? SVT_FRAME_SIZE_NONE : (uint32_t)n;
+}
+
+/* byte t of an uncompressed header whose bits [size_bit, size_bit + 16) (bit 0 = the most significant bit of byte 0) are to say `value`,
+ * most significant bit first: the field's bits of `byte` are replaced, the others kept.  The field lies in the three bytes from
+ * size_bit >> 3 on (in two when size_bit is a multiple of 8): seen as 24 bits it is value << (8 - phase) */
+SVT_HD uint8_t svt_frame_size_field_byte(uint8_t byte, uint32_t t, uint32_t size_bit, uint32_t value) {
+    const uint32_t j = t - (size_bit >> 3);
+    if (j > 2u) return byte;
+    const uint32_t up = 8u - (size_bit & 7u), at = 16u - 8u * j;
+    const uint32_t mask = ((0xFFFFu << up) >> at) & 0xFFu, bits = (((value & 0xFFFFu) << up) >> at) & 0xFFu;
+    return (uint8_t)((byte & ~mask) | bits);
 }
 
 #endif /* SVT_FRAME_CORE_H */

@@ -11,7 +11,7 @@
 #include "../csrc/boolcode_core.h"
 
 uint32_t svt_hip_boolcode_capacity(uint32_t n_bools) {
-    const uint64_t bytes = (7 * ((uint64_t)n_bools + 1 + SVT_BOOL_FRAME_TAIL) + 7) / 8 + 2;
+    const uint64_t bytes = SVT_BOOL_CAPACITY_OF((uint64_t)n_bools);
     return bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
 }
 uint32_t svt_hip_boolcode_bools_capacity(uint32_t n_tokens) {

@@ -2,7 +2,7 @@
  * entropy_host.c -- host-side (plain C) half of the entropy pass (csrc/entropy.hip, rules in csrc/entropy_core.h):
  *   - the limits and the workspace's size, host values;
  *   - svt_hip_entropy_picture: the pass on host pointers -- the stages' host forms in the device entry's order and the same gate text --
- *     the model the GPU tests compare the device entry with;
+ *     the model the GPU tests compare the device entry with; svt_hip_entropy_picture_coef, the same body in the coefficient-update mode;
  *   - svt_hip_entropy_deliverable and svt_hip_compound_refs_from_sign_bias, pure functions of a picture's frame parameters;
  *   - svt_entropy_check_picture, the per-picture checks both forms share.
  */
@@ -73,9 +73,16 @@ static uint64_t stream_bools(const uint32_t *tokens, const svt_bool_segment *seg
     return n;
 }
 
-int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
-                                const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
-                                uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail) {
+/* what the coefficient-update mode refuses of a picture beyond svt_entropy_check_picture: a decoder would store the updated probabilities */
+int32_t svt_entropy_check_picture_coef(const svt_entropy_picture *p) {
+    return !p->frame.error_resilient_mode && p->frame.refresh_frame_context ? SVT_HIP_ERR_BAD_PARAMETER : SVT_HIP_OK;
+}
+
+/* both host forms; coef: the coefficient-update mode, with its second slab beside the first */
+static int32_t entropy_picture(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
+                               const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
+                               uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail, int coef, uint8_t *probs_out,
+                               svt_cu_result *update_out) {
     if (!bool_tables || !pic || !limits || !packet_size || !result || (!packet && packet_capacity)) return SVT_HIP_ERR_BAD_PARAMETER;
     const int32_t  width = pic->frame.width, height = pic->frame.height;
     svt_ent_layout l;
@@ -86,10 +93,25 @@ int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_mo
     if (svt_entropy_check_picture(pic, width, height, header, &header_len)) return SVT_HIP_ERR_BAD_PARAMETER;
     const int intra = svt_ent_intra_only(&pic->frame);
     if (intra ? !modes_tables : !inter_tables) return SVT_HIP_ERR_BAD_PARAMETER;
+    svt_ent_coef_layout cl;
+    svt_cu_picture      cu;
+    uint32_t            size_bit = 0;
+    svt_ent_coef_layout_of(&cl);
+    memset(&cu, 0, sizeof cu);
+    if (coef) { /* the uncompressed header alone, and the compressed header's records round the coefficient section */
+        uint32_t n_prefix = 0, n_suffix = 0;
+        if (svt_entropy_check_picture_coef(pic) || svt_hip_frame_header_uncompressed_host(&pic->frame, header, SVT_FRAME_UNCOMPRESSED_MAX, &header_len, &size_bit) ||
+            svt_hip_frame_header_parts_host(&pic->frame, cu.prefix, &n_prefix, cu.suffix, &n_suffix))
+            return SVT_HIP_ERR_BAD_PARAMETER;
+        cu.n_prefix = (uint16_t)n_prefix; cu.n_suffix = (uint16_t)n_suffix;
+    }
 
-    /* the picture's part of a workspace, in host memory */
-    uint8_t *slab = (uint8_t *)calloc(1, (size_t)l.bytes);
+    /* the picture's part of a workspace, in host memory; in the coefficient-update mode its part of the second slab behind it */
+    uint8_t *slab = (uint8_t *)calloc(1, (size_t)l.bytes + (coef ? (size_t)cl.bytes : 0));
     if (!slab) return SVT_HIP_ERR_NO_RESOURCES;
+    uint8_t *const  slab2 = slab + l.bytes;
+    uint32_t *const cwords = (uint32_t *)(slab2 + cl.words);
+    uint32_t *const counts = !coef || pic->d_counts ? pic->d_counts : (uint32_t *)(slab2 + cl.counts);
     uint32_t *const         tok_off = (uint32_t *)(slab + l.tok_off), *const sb_off = (uint32_t *)(slab + l.sb_off), *const tokens = (uint32_t *)(slab + l.tokens);
     svt_mi_inter_ext *const ext = (svt_mi_inter_ext *)(slab + l.ext);
     uint16_t *const         bools = (uint16_t *)(slab + l.bools);
@@ -100,7 +122,7 @@ int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_mo
     const uint32_t          bools_capacity = intra ? l.kf_bools : l.inter_bools;
     int32_t                 rc;
 
-    const svt_tok_picture tp = {pic->d_lf_mi, pic->d_qcoeff, pic->d_eob_map, tokens, limits->max_tokens, 0, tok_off, sb_off, pic->d_counts};
+    const svt_tok_picture tp = {pic->d_lf_mi, pic->d_qcoeff, pic->d_eob_map, tokens, limits->max_tokens, 0, tok_off, sb_off, counts};
     rc = svt_hip_tokenize_picture(&tp, width, height, mi_stride);
     if (!rc && intra) {
         const svt_modes_picture mp = {pic->d_lf_mi, pic->d_eob_map, tok_off, bools, segs, words + SVT_ENT_W_N_BOOLS, bools_capacity, 0};
@@ -125,6 +147,21 @@ int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_mo
             rc = svt_hip_modes_inter_picture(inter_tables, &ip, width, height, mi_stride);
         }
     }
+    if (!rc && coef) {
+        cu.d_tokens = tokens; cu.d_n_tokens = sb_off + l.n_sb; cu.d_counts = counts; cu.d_eob_branch = (uint32_t *)(slab2 + cl.eob_branch);
+        cu.d_probs = slab2 + cl.probs; cu.d_hdr_bools = (uint16_t *)(slab2 + cl.hdr_bools); cu.d_n_hdr_bools = cwords + SVT_ENT_CW_N_HDR_BOOLS;
+        cu.d_segment = (svt_bool_segment *)(cwords + SVT_ENT_CW_SEGMENT); cu.d_result = (svt_cu_result *)(slab2 + cl.result); cu.max_tokens = limits->max_tokens;
+        rc = svt_hip_coef_update_picture(&cu, bool_tables);
+    }
+    svt_bool_tables *own = NULL; /* the tables with the picture's probabilities */
+    if (!rc && coef) {
+        own = (svt_bool_tables *)malloc(sizeof *own);
+        if (!own) rc = SVT_HIP_ERR_NO_RESOURCES;
+        else {
+            *own = *bool_tables;
+            memcpy(own->coef_probs, cu.d_probs, SVT_CU_PROBS);
+        }
+    }
     uint64_t n_stream = 0;
     if (!rc) {
         /* the gate, phase A: a withheld picture's list is emptied, so that nothing below reads tokens or bools */
@@ -135,18 +172,24 @@ int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_mo
         n_stream = stream_bools(tokens, segs, l.n_segments);
         if (n_stream > limits->max_bools) words[SVT_ENT_W_SIZE] = SVT_BOOL_SIZE_OVERFLOW;
         else
-            rc = svt_hip_boolcode_host(bool_tables, tokens, a ? 0 : (total < limits->max_tokens ? total : limits->max_tokens), bools,
+            rc = svt_hip_boolcode_host(own ? own : bool_tables, tokens, a ? 0 : (total < limits->max_tokens ? total : limits->max_tokens), bools,
                                        a ? 0 : words[SVT_ENT_W_N_BOOLS], segs, l.n_segments, tile, limits->max_tile_bytes, words + SVT_ENT_W_SIZE);
     }
+    if (!rc && coef) /* the compressed header's stream, coded also for a picture that does not ship */
+        rc = svt_hip_boolcode_host(bool_tables, NULL, 0, cu.d_hdr_bools, *cu.d_n_hdr_bools, cu.d_segment, 1, slab2 + cl.hdr_bytes, SVT_ENT_HDR_BYTES,
+                                   cwords + SVT_ENT_CW_HDR_SIZE);
+    free(own);
     if (!rc) {
         /* phase B and the frame stage's rule for one picture */
         const uint32_t coded = words[SVT_ENT_W_SIZE];
         const uint32_t flags = svt_ent_verdict_b(words[SVT_ENT_W_VERDICT], coded, limits->max_tile_bytes);
         words[SVT_ENT_W_SIZE] = svt_ent_result_of(flags, sb_off[l.n_sb], words[SVT_ENT_W_N_BOOLS], coded, svt_ent_status_of(status), result);
-        const uint32_t size = svt_frame_packet_size(header_len, pic->trailer_len, words[SVT_ENT_W_SIZE], limits->max_tile_bytes);
+        const uint32_t comp = coef ? cwords[SVT_ENT_CW_HDR_SIZE] : 0;
+        const uint32_t size = coef ? svt_frame_parts_size(header_len, pic->trailer_len, comp, SVT_ENT_HDR_BYTES, words[SVT_ENT_W_SIZE], limits->max_tile_bytes)
+                                   : svt_frame_packet_size(header_len, pic->trailer_len, words[SVT_ENT_W_SIZE], limits->max_tile_bytes);
         if (detail) {
             detail->stream_bools = n_stream > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n_stream;
-            detail->header_bytes = header_len;
+            detail->header_bytes = header_len + comp;
             detail->coded_size = coded;
             detail->pad_ = 0;
         }
@@ -154,14 +197,39 @@ int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_mo
         if (size != SVT_FRAME_SIZE_NONE) {
             if (size > packet_capacity) rc = SVT_HIP_ERR_BAD_PARAMETER;
             else {
-                memcpy(packet, header, header_len);
-                memcpy(packet + header_len, tile, words[SVT_ENT_W_SIZE]);
-                memcpy(packet + header_len + words[SVT_ENT_W_SIZE], pic->trailer, pic->trailer_len);
+                if (coef) {
+                    for (uint32_t t = 0; t < header_len; t++) packet[t] = svt_frame_size_field_byte(header[t], t, size_bit, comp);
+                    memcpy(packet + header_len, slab2 + cl.hdr_bytes, comp);
+                } else
+                    memcpy(packet, header, header_len);
+                memcpy(packet + header_len + comp, tile, words[SVT_ENT_W_SIZE]);
+                memcpy(packet + header_len + comp + words[SVT_ENT_W_SIZE], pic->trailer, pic->trailer_len);
             }
         }
+        if (coef && probs_out) memcpy(probs_out, cu.d_probs, SVT_CU_PROBS);
+        if (coef && update_out) *update_out = *cu.d_result;
     }
     free(slab);
     return rc;
+}
+
+int32_t svt_hip_entropy_picture(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
+                                const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
+                                uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail) {
+    return entropy_picture(bool_tables, modes_tables, inter_tables, pic, mi_stride, limits, packet, packet_capacity, packet_size, result, detail, 0, NULL, NULL);
+}
+
+int32_t svt_hip_entropy_picture_coef(const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables,
+                                     const svt_entropy_picture *pic, int32_t mi_stride, const svt_entropy_limits *limits, uint8_t *packet, uint32_t packet_capacity,
+                                     uint32_t *packet_size, svt_entropy_result *result, svt_entropy_host_detail *detail, uint8_t *probs, svt_cu_result *update) {
+    return entropy_picture(bool_tables, modes_tables, inter_tables, pic, mi_stride, limits, packet, packet_capacity, packet_size, result, detail, 1, probs, update);
+}
+
+uint64_t svt_hip_entropy_coef_update_bytes(const svt_entropy_limits *limits) {
+    svt_ent_coef_layout cl;
+    if (!limits || limits->max_pics < 1 || limits->max_pics > SVT_FRAME_MAX_PICS || !svt_ent_bools_codable(limits->max_bools)) return 0;
+    svt_ent_coef_layout_of(&cl);
+    return cl.bytes * limits->max_pics;
 }
 
 uint32_t svt_hip_entropy_deliverable(const svt_frame_params *p) {

@@ -9,7 +9,9 @@
  *   - svt_hip_frame_header_parts_host / svt_hip_frame_header_coef_host: the same records in front of and behind update_coef_probs, and the
  *     two headers around a coefficient section that does update (csrc/coef_update.hip), from the same text;
  *   - svt_hip_frame_show_existing_host: the one-byte frame of show_existing_frame;
- *   - svt_hip_frame_assemble_host: the packet layout of csrc/frame_core.h over host pointers, the model of the assembly kernel.
+ *   - svt_hip_frame_assemble_host: the packet layout of csrc/frame_core.h over host pointers, the model of the assembly kernel;
+ *   - svt_hip_frame_header_uncompressed_host and svt_hip_frame_assemble_parts_host: the uncompressed header alone with the place of
+ *     first_part_size, and the model of the three-part assembly that fills it in from the compressed header's size.
  */
 #include <string.h>
 #include "../../include/svtvp9_hip.h"
@@ -208,9 +210,7 @@ static int32_t header_from_bools(const svt_frame_params *p, const uint16_t *bool
     const int32_t          rc = svt_hip_boolcode_host(&no_tables, NULL, 0, bools, n, &seg, 1, out + ub, capacity - ub, &cb);
     if (rc) return rc;
     if (cb > 0xffff || cb > capacity - ub) return SVT_HIP_ERR_BAD_PARAMETER;
-    for (int i = 0; i < 16; i++) /* first_part_size over its place holder */
-        if ((cb >> (15 - i)) & 1u) w.buf[(at + i) >> 3] |= (uint8_t)(0x80u >> ((at + i) & 7));
-    memcpy(out, w.buf, ub);
+    for (uint32_t t = 0; t < ub; t++) out[t] = svt_frame_size_field_byte(w.buf[t], t, at, cb); /* first_part_size over its place holder */
     *uncompressed_bytes = ub;
     *compressed_bytes = cb;
     return SVT_HIP_OK;
@@ -238,6 +238,18 @@ int32_t svt_hip_frame_header_coef_host(const svt_frame_params *p, const uint16_t
                                        uint32_t *uncompressed_bytes, uint32_t *compressed_bytes) {
     if (!p || !hdr_bools || !out || !uncompressed_bytes || !compressed_bytes || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
     return header_from_bools(p, hdr_bools, n_hdr_bools, out, capacity, uncompressed_bytes, compressed_bytes);
+}
+
+int32_t svt_hip_frame_header_uncompressed_host(const svt_frame_params *p, uint8_t *out, uint32_t capacity, uint32_t *bytes, uint32_t *size_bit) {
+    if (!p || !out || !bytes || !size_bit || !params_ok(p)) return SVT_HIP_ERR_BAD_PARAMETER;
+    bit_writer w;
+    memset(&w, 0, sizeof w);
+    const uint32_t at = uncompressed_header(&w, p), ub = (w.bits + 7) >> 3;
+    if (ub > capacity) return SVT_HIP_ERR_BAD_PARAMETER;
+    memcpy(out, w.buf, ub);
+    *bytes = ub;
+    *size_bit = at;
+    return SVT_HIP_OK;
 }
 
 int32_t svt_hip_frame_show_existing_host(int32_t dpb_slot, uint8_t *out) {
@@ -268,6 +280,44 @@ int32_t svt_hip_frame_assemble_host(int32_t n_pics, const svt_frame_packet *pk, 
         uint32_t       n = svt_frame_span(pos, pk[i].header_len, arena_capacity);
         if (n) memcpy(arena + pos, pk[i].header, n);
         pos += pk[i].header_len;
+        n = svt_frame_span(pos, tile, arena_capacity);
+        if (n) memcpy(arena + pos, pk[i].d_tile, n);
+        pos += tile;
+        n = svt_frame_span(pos, pk[i].trailer_len, arena_capacity);
+        if (n) memcpy(arena + pos, pk[i].trailer, n);
+    }
+    table[n_pics].offset = svt_frame_layout(sizes, n_pics, &none);
+    table[n_pics].size = none;
+    return SVT_HIP_OK;
+}
+
+int32_t svt_frame_check_parts(int32_t n_pics, const svt_frame_parts_packet *pk) {
+    if (!pk || n_pics < 1 || n_pics > SVT_FRAME_MAX_PICS) return SVT_HIP_ERR_BAD_PARAMETER;
+    for (int i = 0; i < n_pics; i++)
+        if (!pk[i].d_tile_size || !pk[i].d_compressed_size || (!pk[i].d_tile && pk[i].tile_capacity) || (!pk[i].d_compressed && pk[i].compressed_capacity) ||
+            pk[i].header_len > SVT_FRAME_UNCOMPRESSED_MAX || (uint32_t)pk[i].size_bit + 16 > 8u * pk[i].header_len || pk[i].trailer_len > 4)
+            return SVT_HIP_ERR_BAD_PARAMETER;
+    return SVT_HIP_OK;
+}
+
+int32_t svt_hip_frame_assemble_parts_host(int32_t n_pics, const svt_frame_parts_packet *pk, uint8_t *arena, uint32_t arena_capacity, svt_frame_entry *table) {
+    if (svt_frame_check_parts(n_pics, pk) || !table || (!arena && arena_capacity)) return SVT_HIP_ERR_BAD_PARAMETER;
+    uint32_t sizes[SVT_FRAME_MAX_PICS], none;
+    for (int i = 0; i < n_pics; i++)
+        sizes[i] = svt_frame_parts_size(pk[i].header_len, pk[i].trailer_len, *pk[i].d_compressed_size, pk[i].compressed_capacity, *pk[i].d_tile_size, pk[i].tile_capacity);
+    for (int i = 0; i < n_pics; i++) {
+        const uint32_t off = svt_frame_layout(sizes, i, &none);
+        table[i].offset = off;
+        table[i].size = sizes[i];
+        if (sizes[i] == SVT_FRAME_SIZE_NONE) continue;
+        const uint32_t comp = *pk[i].d_compressed_size, tile = *pk[i].d_tile_size;
+        uint64_t       pos = off;
+        uint32_t       n = svt_frame_span(pos, pk[i].header_len, arena_capacity);
+        for (uint32_t t = 0; t < n; t++) arena[pos + t] = svt_frame_size_field_byte(pk[i].header[t], t, pk[i].size_bit, comp);
+        pos += pk[i].header_len;
+        n = svt_frame_span(pos, comp, arena_capacity);
+        if (n) memcpy(arena + pos, pk[i].d_compressed, n);
+        pos += comp;
         n = svt_frame_span(pos, tile, arena_capacity);
         if (n) memcpy(arena + pos, pk[i].d_tile, n);
         pos += tile;

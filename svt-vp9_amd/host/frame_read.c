@@ -583,13 +583,17 @@ int32_t svt_hip_tile_read_host(const uint8_t *tile, uint32_t size, const svt_til
     return SVT_HIP_OK;
 }
 
-int32_t svt_hip_frame_read_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
-                                int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables,
-                                const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info, svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi,
-                                svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result) {
+/* header and tile; updated: null for the plain reader, which refuses a coefficient update; else a copy of the caller's tables that the
+ * header's updates are applied to and the tile is read with */
+static int32_t frame_read(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
+                          int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables,
+                          const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info, svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi,
+                          svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result, svt_bool_tables *updated) {
     if (!list_ref_frame) return fail(SVT_HIP_ERR_BAD_PARAMETER, "null argument");
-    const int32_t rc = svt_hip_frame_read_header_host(frame, size, last_ref_deltas, last_mode_deltas, info);
+    const int32_t rc = updated ? svt_hip_frame_read_header_coef_host(frame, size, last_ref_deltas, last_mode_deltas, info, updated)
+                               : svt_hip_frame_read_header_host(frame, size, last_ref_deltas, last_mode_deltas, info);
     if (rc) return rc;
+    if (updated) bool_tables = updated;
     if (info->show_existing_frame) return fail(SVT_HIP_ERR_BAD_PARAMETER, "a show-existing frame has no tile");
     const svt_frame_params *p = &info->params;
     svt_tile_read_params par;
@@ -605,4 +609,25 @@ int32_t svt_hip_frame_read_host(const uint8_t *frame, uint32_t size, const int8_
     const uint32_t at = info->uncompressed_bytes + info->compressed_bytes;
     if (at >= size) return fail(SVT_HIP_ERR_BAD_PARAMETER, "the frame ends in front of its tile");
     return svt_hip_tile_read_host(frame + at, size - at, &par, bool_tables, modes_tables, inter_tables, lf_mi, mc_mi, ext, qcoeff, eob_map, result);
+}
+
+int32_t svt_hip_frame_read_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
+                                int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables, const svt_modes_tables *modes_tables,
+                                const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info, svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi,
+                                svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map, svt_tile_read_result *result) {
+    return frame_read(frame, size, last_ref_deltas, last_mode_deltas, mi_stride, restrict_ref_mvs, list_ref_frame, bool_tables, modes_tables, inter_tables, info, lf_mi,
+                      mc_mi, ext, qcoeff, eob_map, result, NULL);
+}
+
+int32_t svt_hip_frame_read_coef_host(const uint8_t *frame, uint32_t size, const int8_t last_ref_deltas[4], const int8_t last_mode_deltas[2], int32_t mi_stride,
+                                     int32_t restrict_ref_mvs, const uint8_t list_ref_frame[2], const svt_bool_tables *bool_tables,
+                                     const svt_modes_tables *modes_tables, const svt_modes_inter_tables *inter_tables, svt_frame_read_info *info,
+                                     svt_lf_mode_info *lf_mi, svt_mc_mode_info *mc_mi, svt_mi_inter_ext *ext, int16_t *qcoeff, uint16_t *eob_map,
+                                     svt_tile_read_result *result, svt_bool_tables *tables_out) {
+    if (!bool_tables) return fail(SVT_HIP_ERR_BAD_PARAMETER, "null argument");
+    svt_bool_tables own = *bool_tables; /* the caller's tables stay what they were */
+    const int32_t   rc = frame_read(frame, size, last_ref_deltas, last_mode_deltas, mi_stride, restrict_ref_mvs, list_ref_frame, bool_tables, modes_tables, inter_tables, info,
+                                    lf_mi, mc_mi, ext, qcoeff, eob_map, result, &own);
+    if (!rc && tables_out) *tables_out = own;
+    return rc;
 }

@@ -3,7 +3,12 @@
 160, the fixture tables): svt_hip_entropy_batch_device for batches of 1 and 16, per stage through the stage hook and for the call, with
 the tokens, mode bools, coded bools and tile bytes of a picture and the device bytes the workspace took under the limits the tool chose.
 
-    python tools/entropy_time.py [--pics 1,16] [--reps 20] [--warmup 3] [--separate]
+    python tools/entropy_time.py [--pics 1,16] [--reps 20] [--warmup 3] [--q 160] [--coef] [--separate]
+
+--coef switches the workspace to the coefficient-update mode (svt_hip_entropy_work_set_coef_update; refresh_frame_context 0, which the
+mode asks for): the stage list then holds "coef_update" between "modes" and "gate", the packets are compared with
+svt_hip_entropy_picture_coef, and packet_bytes_per_picture are the frames tools/coef_update_bytes.py records as "frame, updated".
+--q takes a list of q indexes; the pictures are encoded anew for each.
 
 --separate makes the six existing stage calls over hand-allocated buffers instead (tokeniser, labelling, inter mode info, bool coder,
 frame), under the same limits: it uses nothing of the entropy pass and so also runs on a commit that does not have it.
@@ -88,9 +93,10 @@ def stat(t):
     return dict(median_ms=round(float(np.median(t)), 4), min_ms=round(min(t), 4), max_ms=round(max(t), 4))
 
 
-def frame_params(level):
-    return FM.inter(width=W, height=H, reference_mode=FM.SELECT, allow_comp_inter_inter=1, ref_frame_sign_bias=(0, 0, 0, 1), base_qindex=Q_INDEX, filter_level=level,
-                    frame_parallel_decoding_mode=1)
+def frame_params(level, coef=False):
+    fp = FM.inter(width=W, height=H, reference_mode=FM.SELECT, allow_comp_inter_inter=1, ref_frame_sign_bias=(0, 0, 0, 1), base_qindex=Q_INDEX, filter_level=level,
+                  frame_parallel_decoding_mode=1)
+    return dict(fp, refresh_frame_context=0) if coef else fp
 
 
 def driver(lib, ctx, stream, dp, level, limits, a):
@@ -98,12 +104,15 @@ def driver(lib, ctx, stream, dp, level, limits, a):
     n = len(dp)
     max_tokens, max_bools, max_tile = limits
     lim = E.limits(W, H, n, max_tokens=max_tokens, max_bools=max_bools, max_tile_bytes=max_tile)
-    fp = frame_params(level)
+    fp = frame_params(level, a.coef)
     arr = (B.EntropyPicture * n)(*[E.fill_struct(B.EntropyPicture(), (d.lf_t.data_ptr(), d.mc_t.data_ptr(), d.q_t.data_ptr(), d.emap_t.data_ptr()), fp, LRF, i & 1)
                                    for i, d in enumerate(dp)])
     work = C.c_void_p()
     B.check(lib.svt_hip_entropy_work_create(ctx, W, H, W // 8, C.byref(lim), C.byref(work)))
-    arena = torch.zeros(n * (B.FRAME_HEADER_MAX + max_tile), dtype=torch.uint8, device="cuda")
+    if a.coef:
+        B.check(lib.svt_hip_entropy_work_set_coef_update(ctx, work, 1))
+    header_max = B.FRAME_UNCOMPRESSED_MAX + int(lib.svt_hip_boolcode_capacity(lib.svt_hip_coef_update_bools_capacity())) if a.coef else B.FRAME_HEADER_MAX
+    arena = torch.zeros(n * (header_max + max_tile), dtype=torch.uint8, device="cuda")
     table = torch.zeros(2 * (n + 1), dtype=torch.int32, device="cuda")
     results = torch.zeros(8 * n, dtype=torch.int32, device="cuda")
     marks = {}
@@ -114,8 +123,9 @@ def driver(lib, ctx, stream, dp, level, limits, a):
         marks[stage] = e
     hook = HOOK(on_stage)
     torch.cuda.synchronize()
-    names = B.ENT_STAGES
-    call_ms, hooked_ms, stage_ms = [], [], {s: [] for s in names[:-1]}
+    names = B.ENT_STAGES_COEF
+    order = [0, 1, 2, 3, B.ENT_STAGE_COEF_UPDATE, 4, 5, 6, 7, 8] if a.coef else list(range(9))      # the hook's sequence; the last is "end"
+    call_ms, hooked_ms, stage_ms = [], [], {names[k]: [] for k in order[:-1]}
     for hooked in (False, True):                          # the call alone first; then with an event at every stage boundary
         lib.svt_hip_entropy_work_set_stage_hook(work, hook if hooked else None, None)
         for i in range(a.warmup + a.reps):
@@ -128,8 +138,8 @@ def driver(lib, ctx, stream, dp, level, limits, a):
                 continue
             (hooked_ms if hooked else call_ms).append(e0.elapsed_time(e1))
             if hooked:
-                for k, s in enumerate(names[:-1]):
-                    stage_ms[s].append(marks[k].elapsed_time(marks[k + 1]))
+                for k, nxt in zip(order, order[1:]):
+                    stage_ms[names[k]].append(marks[k].elapsed_time(marks[nxt]))
     res = results.cpu().numpy().view(B.ENTROPY_RESULT_DTYPE)
     tab = table.cpu().numpy().view(np.uint32).reshape(-1, 2)
     assert not res["flags"].any() and int(tab[n, 1]) == 0, ("a picture was withheld", res["flags"].tolist())
@@ -140,14 +150,18 @@ def driver(lib, ctx, stream, dp, level, limits, a):
         pic = dict(W=W, H=H, lf_mi=d.lf_t.cpu().numpy().view(B.LF_MODE_INFO_DTYPE).reshape(H // 8, W // 8),
                    mc_mi=d.mc_t.cpu().numpy().view(B.MC_MODE_INFO_DTYPE).reshape(H // 8, W // 8), qcoeff=d.q_t.cpu().numpy(), eob_map=d.emap_t.cpu().numpy().view(np.uint16),
                    lrf=LRF, restrict=i & 1)
-        h = E.host_entropy(pic, fp, lim)
+        if a.coef:
+            import entropy_coef_model as EC
+            h = EC.host_entropy_coef(pic, fp, lim)
+        else:
+            h = E.host_entropy(pic, fp, lim)
         off, size = (int(v) for v in tab[i])
         assert h["rc"] == 0 and h["packet"] == bytes(arena[off:off + size].cpu().numpy()), "the device's packet differs from the host form's"
         coded.append(h["stream_bools"])
-    out = dict(mode="driver", pictures=n, call=stat(call_ms), call_with_stage_events=stat(hooked_ms), stages={s: stat(t) for s, t in stage_ms.items()},
+    out = dict(mode="driver_coef" if a.coef else "driver", pictures=n, packet_bytes_per_picture=tab[:2, 1].tolist(), call=stat(call_ms), call_with_stage_events=stat(hooked_ms), stages={s: stat(t) for s, t in stage_ms.items()},
                tokens_per_picture=res["tokens"][:2].tolist(), mode_bools_per_picture=res["mode_bools"][:2].tolist(), coded_bools_per_picture=coded,
                tile_bytes_per_picture=res["tile_bytes"][:2].tolist(), inter_leaves=res["inter_leaves"][:2].tolist(), newmv_leaves=res["newmv_leaves"][:2].tolist(),
-               workspace_bytes=int(lib.svt_hip_entropy_work_bytes(W, H, W // 8, C.byref(lim))))
+               workspace_bytes=int(lib.svt_hip_entropy_work_bytes(W, H, W // 8, C.byref(lim))) + (int(lib.svt_hip_entropy_coef_update_bytes(C.byref(lim))) if a.coef else 0))
     lib.svt_hip_entropy_work_destroy(ctx, work)
     return out
 
@@ -196,12 +210,15 @@ def separate(lib, ctx, stream, dp, level, limits, a):
 
 
 def main():
+    global Q_INDEX                  # (tools/coef_update_bytes.py sets it from outside as well)
     ap = argparse.ArgumentParser()
     ap.add_argument("--pics", default="1,16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bools-per-token", type=int, default=2)
     ap.add_argument("--separate", action="store_true")
+    ap.add_argument("--coef", action="store_true")
+    ap.add_argument("--q", default=str(Q_INDEX))
     a = ap.parse_args()
     lib = B.load()
     stream = torch.cuda.Stream()
@@ -210,13 +227,15 @@ def main():
     B.check(lib.svt_hip_boolcode_set_tables(ctx, BM.tables()[1].ctypes.data_as(C.c_void_p)))
     B.check(lib.svt_hip_modes_inter_set_tables(ctx, IM.tables()[1].ctypes.data_as(C.c_void_p)))
     sizes = [int(v) for v in a.pics.split(",")]
-    dp, work, keep, level = encoded_batch(lib, ctx, max(sizes))
-    totals, max_tokens, max_bools, max_tile = sizing(lib, ctx, dp, a.bools_per_token)
-    for n in sizes:
-        out = (separate if a.separate else driver)(lib, ctx, stream, dp[:n], level, (max_tokens, max_bools, max_tile), a)
-        out.update(width=W, height=H, q_index=Q_INDEX, reps=a.reps, limits=dict(max_tokens=max_tokens, max_bools=max_bools, max_tile_bytes=max_tile))
-        print(json.dumps(out), flush=True)
-    lib.svt_hip_encdec_work_destroy(ctx, work)
+    for Q_INDEX in (int(v) for v in a.q.split(",")):
+        dp, work, keep, level = encoded_batch(lib, ctx, max(sizes))
+        totals, max_tokens, max_bools, max_tile = sizing(lib, ctx, dp, a.bools_per_token)
+        for n in sizes:
+            out = (separate if a.separate else driver)(lib, ctx, stream, dp[:n], level, (max_tokens, max_bools, max_tile), a)
+            out.update(width=W, height=H, q_index=Q_INDEX, reps=a.reps, limits=dict(max_tokens=max_tokens, max_bools=max_bools, max_tile_bytes=max_tile))
+            print(json.dumps(out), flush=True)
+        lib.svt_hip_encdec_work_destroy(ctx, work)
+        del dp, keep
     lib.svt_hip_ctx_destroy(ctx)
 
 
